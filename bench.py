@@ -21,17 +21,22 @@ broadcast = all-gather of the build side instead) and the partial Q1 states are 
 the partial aggregates (plans.DistributedQ3): SF 37.5 per rank (SF300 over 8 ranks).
 Per-rank sizes are fixed, so one rank on the 1-GPU box runs the same code path (every collective over one rank).
 
-After the timed region the results of the last step are CHECKED (pair validity, permutation of the probe rows, COUNT /
-SUM values against independent torch reductions) — a wrong result fails the run instead of printing a number.
+A plain run sets up, warms up, times --steps steps and prints the line; it carries `roofline` for the dominant kernel with
+its duration measured by HIP events on the launch stream inside the timed steps.  --dump-outputs DIR writes what the last
+timed step computed as DIR/<name>.npy (dump_outputs below): two builds compared output for output.  The inputs are the
+same from run to run; floating-point sums accumulated by atomics agree to rounding (a few ulp), everything else exactly.
 
-With one GPU the headline line also carries `secondary`: the other BASELINE configurations under the same clock — Q1 over
-code stripes (the reference's own lineitem layout, benchmarks/tpch/create.sql:69-121), the C3 minimal variant, C4 and C5 at
-their per-rank sizes — each with its time, roofline, result check and an oracle cpu_baseline on a bounded sample
-(--no-secondary skips them).
-
-The line carries `roofline` for the dominant kernel with its duration measured by HIP events on the launch stream, and
-`cpu_baseline`: the CPU oracle (a port of the reference algorithms, oracle/) timed on this host's cores on a bounded sample
-of the same workload — 5 trials, mean of trials 2-4 in run order (benchmarks/tpch/process.py:11-45).
+--full adds everything else, after the timed region:
+- the results of the last step are CHECKED (pair validity, permutation of the probe rows, COUNT / SUM values against
+  independent torch reductions) — a wrong result fails the run instead of printing a number;
+- c4 / c5: one more untimed step with HIP events around the device phases of the plan;
+- with one GPU the headline line also carries the probe variants, the operators legs and `secondary`: the other BASELINE
+  configurations under the same clock — Q1 over code stripes (the reference's own lineitem layout,
+  benchmarks/tpch/create.sql:69-121), the C3 minimal variant, C4 and C5 at their per-rank sizes — each with its time,
+  roofline, result check and an oracle cpu_baseline on a bounded sample (--no-secondary skips them);
+- `cpu_baseline`: the CPU oracle (a port of the reference algorithms, oracle/) timed on this host's cores on a bounded
+  sample of the same workload — 5 trials, mean of trials 2-4 in run order (SURVEY.md §8(d),
+  benchmarks/tpch/process.py:11-45).
 """
 import argparse
 import hashlib
@@ -332,6 +337,60 @@ def check_q1(agg_cols, fin, rows):
 
 
 # ------------------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the last timed step computed, in a form that does not depend on the order the kernels wrote it in
+DUMP_SAMPLE_ROWS = 1 << 20
+
+
+def dump_outputs(args, ctx, arrays):
+    """Rank 0 writes every array as DIR/<name>.npy in float64 (every integer written here is below 2^53)."""
+    if args.dump_outputs is None or ctx.rank != 0:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a.astype(np.float64))
+
+
+def seeded_sample(n, dev, seed=11):
+    """A fixed sorted sample of min(n, DUMP_SAMPLE_ROWS) row numbers out of n."""
+    g = torch.Generator(device=dev)
+    g.manual_seed(seed)
+    return torch.sort(torch.randperm(n, device=dev, generator=g)[:DUMP_SAMPLE_ROWS]).values
+
+
+def build_tid_of_probe_rows(ctx, sample, probe_tids, build_tids):
+    """For every sampled (global) probe row, the build row its pair names, -1 for none (the build keys are unique: a probe
+    row has one pair at most).  The pairs of all ranks together."""
+    out = torch.full((sample.numel(),), -1, dtype=torch.int64, device=sample.device)
+    p, b = probe_tids.long(), build_tids.long()
+    pos = torch.searchsorted(sample, p).clamp_(max=sample.numel() - 1)
+    hit = sample[pos] == p
+    out[pos[hit]] = b[hit]
+    if ctx.distributed:
+        dist.all_reduce(out, op=dist.ReduceOp.MAX)
+    return out
+
+
+def q1_groups_in_key_order(fin):
+    """(keys, aggregates) of the finalized Q1 groups, one row per group in (l_returnflag, l_linestatus) order."""
+    keys, vals, _, groups = fin
+    g = int(groups.item())
+    k = torch.stack([keys[0][:g].double(), keys[1][:g].double()], 1)
+    v = torch.stack([vals[a][:g].double() for a in range(len(vals))], 1)
+    order = torch.argsort(k[:, 0] * 256 + k[:, 1])
+    return k[order], v[order]
+
+
+def sorted_row_sample(cols):
+    """A fixed sample of the rows of a column set sorted lexicographically on all columns (last column least significant)."""
+    order = torch.arange(cols[0].numel(), device=cols[0].device)
+    for c in reversed(cols):
+        order = order[torch.sort(c[order], stable=True).indices]
+    rows = order[seeded_sample(order.numel(), order.device)]
+    return torch.stack([c[rows].double() for c in cols], 1)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
 def run_headline(ctx, args):
     dev, rank, world, distributed = ctx.dev, ctx.rank, ctx.world, ctx.distributed
     if distributed:
@@ -419,6 +478,19 @@ def run_headline(ctx, args):
 
     elapsed = timed_loop(ctx, step, args)
     phase_ms = phase_means(recorded, args.steps)
+    if args.dump_outputs is not None:
+        if distributed:
+            pairs = join.materialize(*results["pairs"], results["matches"])
+        else:
+            k = int(results["matches"].item())
+            pairs = (out[0][:k], out[1][:k])
+        sample = seeded_sample(args.probe_rows * world, dev)
+        q1_keys, q1_aggregates = q1_groups_in_key_order(results["fin"])
+        dump_outputs(args, ctx, {"join_matches": [all_sum(ctx, results["matches"].item())],
+                                 "join_probe_rows_sampled": sample,
+                                 "join_build_row_of_sampled_probe_row": build_tid_of_probe_rows(ctx, sample, *pairs),
+                                 "q1_keys": q1_keys, "q1_aggregates": q1_aggregates})
+        del pairs, sample
 
     other_plan_ms = None
     if distributed and world > 1 and args.other_plan_leg:
@@ -465,7 +537,7 @@ def run_headline(ctx, args):
             g_ = int(fin[3].item())
             assert all_sum(ctx, args.agg_rows) == int(fin[1][7][:g_].sum().item()), "merged COUNT(*) != rows of all ranks"
             checks["q1_groups"] = g_
-    assert int(results["groups"].item()) == 4
+        assert int(results["groups"].item()) == 4
 
     rows_per_step = (args.probe_rows + args.agg_rows) * world
     value = rows_per_step * args.steps / elapsed
@@ -650,12 +722,17 @@ def run_c4(ctx, args):
 
     elapsed = timed_loop(ctx, step, args)
     phase_ms = phase_means(recorded, args.steps)
-    # one more (untimed) step with HIP events around the device phases of the plan
-    from quickstep_amd import distributed as qd
-    qd.phases.enabled = True
-    step(False)
-    phase_ms.update({"  " + k: v for k, v in qd.phases.read().items()})
-    qd.phases.enabled = False
+    if args.dump_outputs is not None:
+        # (rank 0's partition of the output relation: orderkey & (P-1) == 0)
+        dump_outputs(args, ctx, {"c4_output_rows": [all_sum(ctx, results["cols"][0].numel())],
+                                 "c4_output_sample_sorted": sorted_row_sample(results["cols"])})
+    if args.full:
+        # one more (untimed) step with HIP events around the device phases of the plan
+        from quickstep_amd import distributed as qd
+        qd.phases.enabled = True
+        step(False)
+        phase_ms.update({"  " + k: v for k, v in qd.phases.read().items()})
+        qd.phases.enabled = False
     cols = results["cols"]
     out_rows = all_sum(ctx, cols[0].numel())
     total_lines = all_sum(ctx, n_l)
@@ -706,11 +783,15 @@ def run_c5(ctx, args):
 
     elapsed = timed_loop(ctx, step, args)
     phase_ms = phase_means(recorded, args.steps)
-    from quickstep_amd import distributed as qd
-    qd.phases.enabled = True          # one more (untimed) step with HIP events around the phases of the plan
-    step(False)
-    phase_ms.update({"  " + k: v for k, v in qd.phases.read().items()})
-    qd.phases.enabled = False
+    if args.dump_outputs is not None:
+        dump_outputs(args, ctx, {"q3_joined_pairs_and_groups": [all_sum(ctx, results["pairs"]), all_sum(ctx, results["groups"])],
+                                 "q3_top10_orderkey": results["top_keys"], "q3_top10_revenue": results["top_revenue"]})
+    if args.full:
+        from quickstep_amd import distributed as qd
+        qd.phases.enabled = True          # one more (untimed) step with HIP events around the phases of the plan
+        step(False)
+        phase_ms.update({"  " + k: v for k, v in qd.phases.read().items()})
+        qd.phases.enabled = False
     rows_rank = inputs["c_custkey"].numel() + inputs["o_orderkey"].numel() + inputs["l_orderkey"].numel()
     rows = all_sum(ctx, rows_rank)
     pairs = all_sum(ctx, results["pairs"])
@@ -1193,7 +1274,7 @@ def partitioned_operators_leg(args, config, size, twin_ms):
 def secondary_c4(ctx, args, threads):
     from quickstep_amd import plans
     sub = argparse.Namespace(**vars(args))
-    sub.steps, sub.warmup = args.secondary_steps, 2
+    sub.steps, sub.warmup, sub.dump_outputs = args.secondary_steps, 2, None
     out = condensed(run_c4(ctx, sub))
     if not args.no_operators:
         torch.cuda.empty_cache()
@@ -1233,7 +1314,7 @@ def secondary_c4(ctx, args, threads):
 def secondary_c5(ctx, args, threads):
     from quickstep_amd import plans
     sub = argparse.Namespace(**vars(args))
-    sub.steps, sub.warmup = args.secondary_steps, 2
+    sub.steps, sub.warmup, sub.dump_outputs = args.secondary_steps, 2, None
     out = condensed(run_c5(ctx, sub))
     if not args.no_operators:
         torch.cuda.empty_cache()
@@ -1467,7 +1548,15 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="launch check without a GPU: the ranks rendezvous over gloo, agree on the world size and rank 0 prints a "
                          "line with no measurement in it (tests/test_bench_launch.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the result checks, the probe variants, the operators legs, "
+                         "`secondary`, the cpu baselines and the per-phase pass of c4 / c5 (a plain run only times its steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last step computed to DIR/<name>.npy (float64, a fixed sample of "
+                         "the join's pairs)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_check = args.no_probe_variants = args.no_secondary = args.no_operators = args.no_cpu_baseline = True
 
     ctx = Ctx()
     ctx.world = world = int(os.environ.get("WORLD_SIZE", "1"))

@@ -59,7 +59,7 @@ def _rehearsal(world, config, transport, sizes):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update({"QSX_BENCH_SHARED_GPU": "1", "QSX_RCCL_LIBRARY": lib, "QSX_ALLOW_TEST_TRANSPORT": "1"})
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--transport", transport, "--config", config,
-                        "--steps", "1", "--warmup", "0", "--no-cpu-baseline"] + sizes, env=env, capture_output=True, text=True, timeout=900)
+                        "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline"] + sizes, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric')][-1])
     assert line["n_gpus"] == world and line["world_size_seen"] == world and line["self_launched"] is True
@@ -116,9 +116,50 @@ def test_a_failing_c_abi_leg_falls_back_to_the_torch_leg(how):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update({"QSX_BENCH_SHARED_GPU": "1", "QSX_RCCL_LIBRARY": lib, "QSX_ALLOW_TEST_TRANSPORT": "1", "QSX_BENCH_BREAK_CAPI_LEG": how})
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--transport", "both", "--config", "c4", "--steps", "1",
-                        "--warmup", "0", "--no-cpu-baseline", "--capi-leg-deadline", "20"] + SMALL["c4"], env=env, capture_output=True,
+                        "--warmup", "0", "--full", "--no-cpu-baseline", "--capi-leg-deadline", "20"] + SMALL["c4"], env=env, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric')][-1])
     assert line["transport"] == "torch" and "error" in line["transport_legs"]["capi"] and line["value"] > 0
     assert line["n_gpus"] == 2 and line["world_size_seen"] == 2
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_steps_outputs(dev, tmp_path):
+    """A plain `bench.py` run: the headline line without the --full legs, --steps timed steps, and --dump-outputs writing the
+    last step's results — checked against the inputs regenerated here from the bench's own seeds."""
+    import numpy as np
+    import torch
+    build_rows, probe_rows, agg_rows = 200_000, 4_000_000, 8_000_000
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--build-rows", str(build_rows), "--probe-rows", str(probe_rows), "--agg-rows", str(agg_rows),
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric')][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["higher_is_better"] is True
+    assert line["unit"] == "rows/s" and line["dtype"] == "i32 keys / f64 sums"
+    assert not {"secondary", "operators", "cpu_baseline"} & set(line) and "variants" not in line["probe"]
+
+    out = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert all(a.dtype == np.float64 for a in out.values()) and sum(a.nbytes for a in out.values()) <= 64 << 20
+    # the join: every sampled probe row's pair names the build row that holds its key
+    g = torch.Generator(device=dev)
+    g.manual_seed(2)
+    build_keys = torch.randperm(build_rows, device=dev, generator=g, dtype=torch.int32)
+    g.manual_seed(3)
+    probe_keys = torch.randint(0, build_rows, (probe_rows,), device=dev, generator=g, dtype=torch.int32)
+    row_of_key = torch.empty(build_rows, dtype=torch.int64, device=dev)
+    row_of_key[build_keys.long()] = torch.arange(build_rows, device=dev)
+    sample = torch.from_numpy(out["join_probe_rows_sampled"].astype(np.int64)).to(dev)
+    assert sample.numel() == min(probe_rows, 1 << 20) and bool((sample[1:] > sample[:-1]).all())
+    want = row_of_key[probe_keys[sample].long()].cpu().numpy()
+    assert np.array_equal(out["join_build_row_of_sampled_probe_row"], want.astype(np.float64))
+    assert out["join_matches"].tolist() == [probe_rows]
+    # the aggregation: the four groups in key order, COUNT(*) per group against a count of the regenerated rows
+    import bench
+    k1, k2 = bench.gen_q1_columns_gpu(agg_rows, dev, 4)[:2]
+    combos, counts = torch.unique(k1.long() * 256 + k2.long(), return_counts=True)
+    keys, aggs = out["q1_keys"], out["q1_aggregates"]
+    assert keys.shape == (4, 2) and aggs.shape == (4, 8)
+    assert np.array_equal(keys[:, 0] * 256 + keys[:, 1], combos.cpu().numpy().astype(np.float64))
+    assert np.array_equal(aggs[:, 7], counts.cpu().numpy().astype(np.float64))

@@ -155,6 +155,26 @@ __global__ void publish_control_kernel(const unsigned long long *__restrict__ co
 // finalize
 // ---------------------------------------------------------------------------
 
+// AVG = SUM / COUNT, rounded once (ties to even) like the reference's double division.  The f64 divide the compiler emits
+// (v_div_scale_f64, v_rcp_f64, v_fma_f64 refinement, v_div_fmas_f64, v_div_fixup_f64) can round a quotient among the subnormals
+// twice: -89914724021171 x 2^-1074 / 98, a tie at -917497183889.5 units of 2^-1074, came back as ...889 instead of ...890.  Its
+// result is within one unit of the exact quotient, so the nearest of it and its two neighbours is the correctly rounded one.
+// The remainders s - q c are exact (fma): they are multiples of 2^-1074 far below 2^-1021.
+__device__ __forceinline__ double avg_quotient(double s, double c) {
+  const double q = s / c;
+  if (!isfinite(q) || fabs(q) >= 2.2250738585072014e-308) return q;   // normal quotients: one rounding already
+  double best = q, best_r = fabs(fma(-q, c, s));
+  const double around[2] = {nextafter(q, -INFINITY), nextafter(q, INFINITY)};
+  for (const double x : around) {
+    const double r = fabs(fma(-x, c, s));
+    if (r < best_r || (r == best_r && (__double_as_longlong(x) & 1) == 0)) {
+      best = x;
+      best_r = r;
+    }
+  }
+  return best;
+}
+
 __device__ __forceinline__ void write_values(const FinalizeDesc &f, const unsigned long long *states,
                                              unsigned long long col_stride, unsigned long long idx,
                                              int count_col, bool empty_group, long long out_row) {
@@ -194,7 +214,7 @@ __device__ __forceinline__ void write_values(const FinalizeDesc &f, const unsign
         const double sum = f.is_int[a] ? static_cast<double>(static_cast<long long>(raw))
                                        : __longlong_as_double(static_cast<long long>(raw));
         is_null = seen == 0;
-        static_cast<double *>(f.out_vals[a])[out_row] = is_null ? 0.0 : sum / static_cast<double>(seen);
+        static_cast<double *>(f.out_vals[a])[out_row] = is_null ? 0.0 : avg_quotient(sum, static_cast<double>(seen));
       }
     }
     if (f.out_nulls[a] != nullptr) f.out_nulls[a][out_row] = is_null ? 1 : 0;

@@ -606,10 +606,10 @@ typedef enum qsx_agg_strategy {
 
 typedef enum qsx_agg_fn {
   QSX_AGG_COUNT_STAR = 0, /* COUNT(*)            -> int64 */
-  QSX_AGG_SUM = 1,        /* SUM(int|long) -> int64 ; SUM(float|double|expr) -> double */
+  QSX_AGG_SUM = 1,        /* SUM(int|long|integer expr) -> int64 ; SUM(float|double|double expr) -> double */
   QSX_AGG_AVG = 2,        /* sum / (double)count -> double (AggregationHandleAvg.cpp:144-155) */
   QSX_AGG_MIN = 3,        /* AggregationHandleMin.cpp:45-120: result has the argument's type   */
-  QSX_AGG_MAX = 4,        /* AggregationHandleMax.cpp:45-120  (DOUBLE for an expression)       */
+  QSX_AGG_MAX = 4,        /* AggregationHandleMax.cpp:45-120  (DOUBLE for a double expression) */
   QSX_AGG_COUNT = 5       /* COUNT(x): rows whose argument is not NULL -> int64 (AggregationHandleCount.hpp:98-118,
                              the count_star = false, nullable_type = true instantiation) */
 } qsx_agg_fn_t;
@@ -627,7 +627,9 @@ typedef struct qsx_operand {
 } qsx_operand_t;
 
 typedef enum qsx_expr_op {
-  QSX_EX_ADD = 0, QSX_EX_SUB = 1, QSX_EX_MUL = 2, QSX_EX_DIV = 3
+  QSX_EX_ADD = 0, QSX_EX_SUB = 1, QSX_EX_MUL = 2, QSX_EX_DIV = 3,
+  /* the same four in INTEGER arithmetic (below) */
+  QSX_EX_IADD = 4, QSX_EX_ISUB = 5, QSX_EX_IMUL = 6, QSX_EX_IDIV = 7
 } qsx_expr_op_t;
 
 /* temp[dst] = a OP b, evaluated per row in IEEE double, operands converted
@@ -635,7 +637,28 @@ typedef enum qsx_expr_op {
  * types/operations/binary_operations/ArithmeticBinaryOperators.hpp:203-340).
  * This replaces the temporary NativeColumnVectors of
  * ScalarBinaryExpression::getAllValues (expressions/scalar/
- * ScalarBinaryExpression.cpp:100-195) — fused, nothing is materialised. */
+ * ScalarBinaryExpression.cpp:100-195) — fused, nothing is materialised.
+ *
+ * QSX_EX_IADD .. QSX_EX_IDIV evaluate in integer arithmetic, as the reference instantiates + - * / on integer argument
+ * types (the same header) and as qsx_eval_expression_long does:
+ *   operands   a COLUMN of type INT or LONG (plain, code-compressed or nullable like any other); a TEMP that an earlier
+ *              integer instruction produced; a CONST whose consts[] double is integral with |c| <= 2^53 — an INT operand when
+ *              it fits 32 bits, else a LONG.  Anything else (a FLOAT / DOUBLE / CHAR / DATE column, a temp of a double
+ *              instruction, a non-integral constant) is QSX_ERR_INVALID_ARGUMENT from qsx_agg_state_create: there is no
+ *              implicit double -> integer conversion.
+ *   result     INT when both operands are INT: computed in 64 bits and wrapped to 32 (two's complement); otherwise LONG,
+ *              wrapped to 64.  IDIV truncates toward zero; x / 0 = 0; x / -1 = 0 - x wrapped (INT64_MIN / -1 = INT64_MIN,
+ *              and as INTs INT32_MIN / -1 = INT32_MIN).  A temp redefined by a later instruction has the type of its latest
+ *              definition.
+ *   mixing     a double instruction may read an integer temp: it is converted to double like an INT / LONG column.
+ *              Programs without integer instructions behave bit for bit as before.
+ *   aggregates over an integer temp: SUM accumulates and finalizes as int64; AVG is double(sum) / double(count), rounded
+ *              once like AVG over an integer column; MIN / MAX compare as integers and the output column has the temp's
+ *              type and width (INT: 4 bytes, LONG: 8); COUNT(x) as ever.  A temp is NULL when any operand is.
+ *              qsx_agg_state_image_layout reports QSX_ACC_SUM_I64 / MIN_I64 / MAX_I64 for these columns.
+ *   DISTINCT   over an expression evaluates through qsx_eval_expression, in double: integer instructions are refused there.
+ * A library built before these four existed answers such a configuration with QSX_ERR_INVALID_ARGUMENT: that is how a
+ * caller detects the capability (QSX_ABI_VERSION did not change). */
 typedef struct qsx_expr_instr {
   int32_t op;
   int32_t dst; /* 0 .. QSX_MAX_TEMPS-1 */
@@ -682,7 +705,8 @@ int qsx_eval_expression(int num_columns, const void *const *cols, const int32_t 
  * argument types (types/operations/binary_operations/ArithmeticBinaryOperators.hpp:203-340): INT op INT is an INT (32-bit
  * wrap-around), an operation with a LONG operand a LONG; `/` truncates toward zero, x / 0 gives 0.  consts: host array of
  * QSX_MAX_CONSTS int64 (a constant that fits 32 bits counts as an INT operand).  out_width 4 or 8: the result stripe holds
- * INT or LONG values (the caller knows the expression's type by the same rule). */
+ * INT or LONG values (the caller knows the expression's type by the same rule).  QSX_EX_IADD .. IDIV are accepted as synonyms
+ * of the plain ops, so that one flattened program serves this entry point and an aggregation. */
 int qsx_eval_expression_long(int num_columns, const void *const *cols, const int32_t *types, int num_instrs,
                              const qsx_expr_instr_t *instrs, const int64_t *consts, qsx_operand_t result, int64_t n, int out_width,
                              void *out_dev, qsx_stream_t stream);

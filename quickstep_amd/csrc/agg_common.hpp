@@ -18,6 +18,12 @@ struct DevOperand {
 // Internal operand kind (never in a qsx_agg_config_t): word `index` of a wide group-by key, see DevConfig::wide_words.
 constexpr int kOpdKeyWord = 100;
 constexpr int kMaxKeyWords = 3;
+// Internal operand kind: a temp that an integer instruction (QSX_EX_IADD .. IDIV) produced.  Its 8-byte slot holds the
+// int64 bits of the value (an INT result sign-extended); a double instruction that reads it converts like an INT / LONG column.
+constexpr int kOpdIntTemp = 101;
+// Internal flag in DevInstr::op of an integer instruction whose operands are both INT: the result wraps to 32 bits.
+constexpr int kExNarrow = 0x100;
+__host__ __device__ constexpr bool is_temp_kind(int kind) { return kind == QSX_OPD_TEMP || kind == kOpdIntTemp; }
 struct DevInstr {
   int op;
   int dst;
@@ -31,7 +37,7 @@ enum AccKind { kAccSumF64 = 0, kAccSumI64 = 1, kAccMinI64 = 2, kAccMaxI64 = 3 };
 
 struct DevSum {
   DevOperand arg;
-  int is_int;   // the argument is an INT/LONG column (read as integer)
+  int is_int;   // the argument is an INT/LONG column or an integer temp (read as integer)
   int kind;     // AccKind
   // Nullable inputs: bit s set = the argument is NULL when null slot s (DevConfig::null_column) is NULL in the row; the
   // row then contributes the accumulator's identity.  count_valid: this accumulator counts the rows whose mask is
@@ -58,7 +64,10 @@ struct DevPred {
 // operands pre-resolved to LDS byte offsets so that an interpreted instruction is one scalar
 // decode + V ds_read_b64 per operand + V ds_write_b64, with no per-row type dispatch and no VGPR
 // array of temps (which capped the interpreter at V = 2 rows per thread).
-enum PlanMode { kPlanTileF64 = 0, kPlanTempF64 = 1, kPlanImm = 2, kPlanTileI32 = 3, kPlanTileI64 = 4, kPlanTileF32 = 5 };
+// (kPlanImmI64 / kPlanTempI64: operand of an integer instruction — the immediate's int64 bits travel in `imm` — and an
+// integer temp's slot, read as int64)
+enum PlanMode { kPlanTileF64 = 0, kPlanTempF64 = 1, kPlanImm = 2, kPlanTileI32 = 3, kPlanTileI64 = 4, kPlanTileF32 = 5,
+                kPlanImmI64 = 6, kPlanTempI64 = 7 };
 struct PlanOperand {
   int mode;    // PlanMode
   int off;     // byte offset inside the staged tile / the temps area
@@ -70,7 +79,7 @@ struct PlanInstr {
   PlanOperand a, b;
 };
 struct PlanSum {
-  int is_int;   // integer column argument: read `width` bytes at tile + arg.off
+  int is_int;   // integer argument: read `width` bytes at tile + arg.off (a column) or 8 at temps + arg.off (kPlanTempI64)
   int width;
   PlanOperand arg;
 };

@@ -170,6 +170,7 @@ inline FactoredStatic factored_analyse(const DevConfig &d, bool dense) {
   Node temps[QSX_MAX_TEMPS] = {};
   unsigned expr_carriers = 0;   // plain columns that occur inside expressions (their planes are f64)
   for (int k = 0; k < d.num_instrs; ++k) {
+    if (d.instrs[k].op >= QSX_EX_IADD) return f;   // integer arithmetic: the coefficients are doubles — the decoding kernels answer
     Node a{}, b{};
     if (!leaf(d.instrs[k].a, temps, &a) || !leaf(d.instrs[k].b, temps, &b)) return f;
     Node r{0, a.dmask | b.dmask, a.cmask | b.cmask};

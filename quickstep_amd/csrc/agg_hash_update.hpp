@@ -361,6 +361,88 @@ __device__ __forceinline__ void operand_vec(const DevConfig &c, const DevOperand
       break;
   }
 }
+// The same for a program with integer instructions: a double instruction that reads an integer temp converts it like an
+// INT / LONG column.
+template <int V, int BLOCK = kABlock, bool kDec = false>
+__device__ __forceinline__ void operand_vec_mixed(const DevConfig &c, const DevOperand &o, const Temps<V> &s,
+                                                  const char *tile, int trow, double (&out)[V], const DecodedRows<V> *dec = nullptr) {
+  if (o.kind == kOpdIntTemp) {
+    temps_get<V>(s, o.index, out);
+#pragma unroll
+    for (int v = 0; v < V; ++v) out[v] = static_cast<double>(__double_as_longlong(out[v]));
+    return;
+  }
+  operand_vec<V, BLOCK, kDec>(c, o, s, tile, trow, out, dec);
+}
+
+// ---- integer instructions (QSX_EX_IADD .. IDIV, include/qsx.h) -------------------------------------------------------
+// One node: 64-bit two's complement, wrapped to 32 bits when both operands are INT (kExNarrow; the low word of a 64-bit
+// + - * is that of the 32-bit operation, and an INT quotient computed in 64 bits is exact but for INT32_MIN / -1, which wraps
+// to INT32_MIN as it should).  x / 0 = 0 and x / -1 = 0 - x: the rules of eval_expression_long_kernel.
+__device__ __forceinline__ long long int_node(int op, long long a, long long b) {
+  const unsigned long long ua = static_cast<unsigned long long>(a), ub = static_cast<unsigned long long>(b);
+  long long r;
+  switch (op & 3) {
+    case QSX_EX_ADD: r = static_cast<long long>(ua + ub); break;
+    case QSX_EX_SUB: r = static_cast<long long>(ua - ub); break;
+    case QSX_EX_MUL: r = static_cast<long long>(ua * ub); break;
+    default:
+      if ((op & kExNarrow) != 0) {   // both operands are sign-extended INTs: a 32-bit division
+        const int32_t a32 = static_cast<int32_t>(a), b32 = static_cast<int32_t>(b);
+        r = b32 == 0 ? 0 : (b32 == -1 ? static_cast<long long>(0u - static_cast<uint32_t>(a32)) : static_cast<long long>(a32 / (b32 == 0 || b32 == -1 ? 1 : b32)));   // (the divisor of the unused arm is 1)
+      } else {
+        r = b == 0 ? 0 : (b == -1 ? static_cast<long long>(0ull - ua) : a / (b == 0 || b == -1 ? 1 : b));
+      }
+      break;
+  }
+  if ((op & kExNarrow) != 0) r = static_cast<long long>(static_cast<int32_t>(r));
+  return r;
+}
+// Operand of an integer instruction, compiled form: a column (INT sign-extended), an integral constant, an integer temp's bits.
+template <int V, int BLOCK = kABlock, bool kDec = false>
+__device__ __forceinline__ void operand_int_vec(const DevConfig &c, const DevOperand &o, const Temps<V> &s, const char *tile, int trow,
+                                                long long (&out)[V], const DecodedRows<V> *dec = nullptr) {
+  switch (o.kind) {
+    case QSX_OPD_COLUMN:
+#pragma unroll
+      for (int v = 0; v < V; ++v) out[v] = tile_int<V, kDec>(c, tile, o.index, trow + v * BLOCK, dec, v);
+      break;
+    case QSX_OPD_CONST:
+#pragma unroll
+      for (int v = 0; v < V; ++v) out[v] = static_cast<long long>(c.consts[o.index]);   // (integral: agg_translate.hpp)
+      break;
+    default: {
+      double bits[V];
+      temps_get<V>(s, o.index, bits);
+#pragma unroll
+      for (int v = 0; v < V; ++v) out[v] = __double_as_longlong(bits[v]);
+      break;
+    }
+  }
+}
+// The same for the interpreter (plan_interpreter() resolves an integer instruction's operands to these modes only).
+template <int V, int BLOCK = kABlock>
+__device__ __forceinline__ void plan_operand_int_vec(const PlanOperand &o, const char *tile, const char *temps, int trow,
+                                                     long long (&out)[V]) {
+  switch (o.mode) {
+    case kPlanImmI64:
+#pragma unroll
+      for (int v = 0; v < V; ++v) out[v] = __double_as_longlong(o.imm);
+      break;
+    case kPlanTileI32: {
+      const int32_t *p = reinterpret_cast<const int32_t *>(tile + o.off);
+#pragma unroll
+      for (int v = 0; v < V; ++v) out[v] = p[trow + v * BLOCK];
+      break;
+    }
+    default: {  // LONG column of the tile or integer temp slot
+      const long long *p = reinterpret_cast<const long long *>((o.mode == kPlanTempI64 ? temps : tile) + o.off);
+#pragma unroll
+      for (int v = 0; v < V; ++v) out[v] = p[trow + v * BLOCK];
+      break;
+    }
+  }
+}
 
 // Interpreter operand: everything is resolved to (mode, LDS byte offset | immediate).
 template <int V, int BLOCK = kABlock>
@@ -377,8 +459,9 @@ __device__ __forceinline__ void plan_operand_vec(const PlanOperand &o, const cha
       for (int v = 0; v < V; ++v) out[v] = static_cast<double>(p[trow + v * BLOCK]);
       break;
     }
-    case kPlanTileI64: {
-      const long long *p = reinterpret_cast<const long long *>(tile + o.off);
+    case kPlanTileI64:
+    case kPlanTempI64: {   // (an integer temp read by a double instruction)
+      const long long *p = reinterpret_cast<const long long *>((o.mode == kPlanTempI64 ? temps : tile) + o.off);
 #pragma unroll
       for (int v = 0; v < V; ++v) out[v] = static_cast<double>(p[trow + v * BLOCK]);
       break;
@@ -631,8 +714,10 @@ __device__ __forceinline__ void classify_row(bool live, unsigned long long code,
 // workgroup is done with its tiles, in front of the flush.  Measured: the LDS atomics disappear
 // (SQ_LDS_ADDR_CONFLICT 9e7 -> 4e5 cycles) but every (row, entry) pair executes its block of adds whenever any lane of the
 // wave matches (4x the f64 adds) and the registers cost a workgroup per CU: slower than the atomics it replaces.
+// kIntExpr: the program may hold integer instructions (QSX_EX_IADD .. IDIV).  The interpreter always can; a compiled shape
+// says so (agg_jit.hip), and every shape without them compiles exactly the code it compiled before they existed.
 template <bool kStatic, bool kDense, int NS, int V, bool kDir = false, int BLOCK = kABlock, bool kDirBuild = false, bool kRuns = false,
-          int REG = 0>
+          int REG = 0, bool kIntExpr = !kStatic>
 __device__ __forceinline__ void agg_hash_update_body(const DevConfig &c, const void *const *cols, const void *const *dicts, int64_t n,
                                                      const uint64_t *__restrict__ filter, const HashTableView &g,
                                                      const DenseView &dense, int S, int rep_shift, int nbuf,
@@ -1157,6 +1242,17 @@ __device__ __forceinline__ void agg_hash_update_body(const DevConfig &c, const v
       // interpreter: operands and results live in LDS (plan_instrs), nothing of the program in VGPRs
       for (int k = 0; k < c.num_instrs; ++k) {
         const PlanInstr in = c.plan_instrs[k];
+        if (in.op >= QSX_EX_IADD) {   // integer instruction (the flag bits above the op included)
+          long long ia[V], ib[V];
+          plan_operand_int_vec<V, BLOCK>(in.a, tile, lds_temps, trow, ia);
+          plan_operand_int_vec<V, BLOCK>(in.b, tile, lds_temps, trow, ib);
+          if (in.dst_off >= 0) {
+            long long *dst = reinterpret_cast<long long *>(lds_temps + in.dst_off);
+#pragma unroll
+            for (int v = 0; v < V; ++v) dst[trow + v * BLOCK] = int_node(in.op, ia[v], ib[v]);
+          }
+          continue;
+        }
         double a[V], b[V], res[V];
         plan_operand_vec<V, BLOCK>(in.a, tile, lds_temps, trow, a);
         plan_operand_vec<V, BLOCK>(in.b, tile, lds_temps, trow, b);
@@ -1188,8 +1284,22 @@ __device__ __forceinline__ void agg_hash_update_body(const DevConfig &c, const v
     cfg_for<kStatic, QSX_MAX_INSTRS>(kStatic ? c.num_instrs : 0, [&](int k) __attribute__((always_inline)) {
       const DevInstr in = c.instrs[k];
       double a[V], b[V], res[V];
-      operand_vec<V, BLOCK, kStatic>(c, in.a, temps, tile, trow, a, dec);
-      operand_vec<V, BLOCK, kStatic>(c, in.b, temps, tile, trow, b, dec);
+      if constexpr (kIntExpr) {
+        if (in.op >= QSX_EX_IADD) {   // (a constant here: the node costs its integer instructions and nothing else)
+          long long ia[V], ib[V];
+          operand_int_vec<V, BLOCK, kStatic>(c, in.a, temps, tile, trow, ia, dec);
+          operand_int_vec<V, BLOCK, kStatic>(c, in.b, temps, tile, trow, ib, dec);
+#pragma unroll
+          for (int v = 0; v < V; ++v) res[v] = __longlong_as_double(int_node(in.op, ia[v], ib[v]));
+          temps_set<V>(temps, in.dst, res);
+          return;
+        }
+        operand_vec_mixed<V, BLOCK, kStatic>(c, in.a, temps, tile, trow, a, dec);
+        operand_vec_mixed<V, BLOCK, kStatic>(c, in.b, temps, tile, trow, b, dec);
+      } else {
+        operand_vec<V, BLOCK, kStatic>(c, in.a, temps, tile, trow, a, dec);
+        operand_vec<V, BLOCK, kStatic>(c, in.b, temps, tile, trow, b, dec);
+      }
       switch (in.op) {
         case QSX_EX_ADD:
 #pragma unroll
@@ -1225,14 +1335,19 @@ __device__ __forceinline__ void agg_hash_update_body(const DevConfig &c, const v
 #pragma unroll
         for (int v = 0; v < V; ++v) inc[v] = key_word_of<V, kStatic>(c, tile, s.arg.index, trow + v * BLOCK, dec, v);
       } else if (s.is_int) {
-        if constexpr (kStatic) {
+        if constexpr (kStatic && kIntExpr) {
+          long long x[V];
+          operand_int_vec<V, BLOCK, kStatic>(c, s.arg, temps, tile, trow, x, dec);   // a column or an integer temp
+#pragma unroll
+          for (int v = 0; v < V; ++v) inc[v] = static_cast<unsigned long long>(x[v]);
+        } else if constexpr (kStatic) {
 #pragma unroll
           for (int v = 0; v < V; ++v) {
             inc[v] = static_cast<unsigned long long>(tile_int<V, kStatic>(c, tile, s.arg.index, trow + v * BLOCK, dec, v));
           }
         } else {
           const PlanSum ps = c.plan_sums[j];
-          const char *p = tile + ps.arg.off;
+          const char *p = (ps.arg.mode == kPlanTempI64 ? lds_temps : tile) + ps.arg.off;
 #pragma unroll
           for (int v = 0; v < V; ++v) {
             const int r = trow + v * BLOCK;

@@ -125,6 +125,10 @@ std::string compiler_driver();   // (below: who compiles the shapes — empty = 
 
 std::string make_source(const DevConfig &dev, int num_sums, bool dense, const JitGeometry &geo) {
   std::ostringstream o;
+  // a program with integer instructions asks for the body's kIntExpr (its last template argument, behind REG); every other
+  // shape's text is what it was before they existed
+  bool int_expr = false;
+  for (int k = 0; k < dev.num_instrs; ++k) int_expr = int_expr || dev.instrs[k].op >= QSX_EX_IADD;
   bool any_coded = false;   // unused pointers are passed as literals: every live scalar argument costs SGPRs in the tile loop
   for (int i = 0; i < dev.num_columns; ++i) any_coded = any_coded || dev.code_width[i] != 0;
   // a state over nullable columns: the null bitmaps of a call arrive as a device table of num_null_cols pointers (by null
@@ -143,7 +147,7 @@ std::string make_source(const DevConfig &dev, int num_sums, bool dense, const Ji
       << "  static constexpr DevConfig D = jit_make_dev();\n"
       << "  (void)cols; (void)pieces;\n"
       << "  agg_hash_update_body<true, true, " << num_sums << ", " << (geo.dir_rows > 1 ? geo.dir_rows : 1) << ", true, " << kDirBlock << ", false, "
-      << (geo.runs != 0 ? "true" : "false")
+      << (geo.runs != 0 ? "true" : "false") << (int_expr ? ", 0, true" : "")
       << ">(D, " << (geo.runs != 0 ? "nullptr" : "cols.p") << ", " << (any_coded ? "dicts" : "nullptr") << ", n, "
       << (dev.filter_lds_off >= 0 ? "filter" : "nullptr") << ", HashTableView{}, view, " << geo.S << ", " << geo.rep_shift << ", " << geo.nbuf
       << ", " << geo.ranges << ", pieces, " << nulls_arg << ", nullptr);\n}\n}  // namespace qsx\n";
@@ -158,7 +162,7 @@ std::string make_source(const DevConfig &dev, int num_sums, bool dense, const Ji
       << "  static constexpr DevConfig D = jit_make_dev();\n"
       << "  (void)cols; (void)pieces;\n"
       << "  agg_hash_update_body<true, false, " << num_sums << ", " << (geo.dir_rows == 2 ? 2 : 1) << ", true, " << kDirBlock << ", false, "
-      << (geo.runs != 0 ? "true" : "false")
+      << (geo.runs != 0 ? "true" : "false") << (int_expr ? ", 0, true" : "")
       << ">(D, " << (geo.runs != 0 ? "nullptr" : "cols.p") << ", " << (any_coded ? "dicts" : "nullptr") << ", n, "
       << (dev.filter_lds_off >= 0 ? "filter" : "nullptr") << ", view, DenseView{}, " << geo.dir_gids << ", 0, " << geo.nbuf << ", 1, "
       << (geo.runs != 0 ? "pieces" : "nullptr") << ", " << nulls_arg << ", &d);\n}\n}  // namespace qsx\n";
@@ -168,9 +172,10 @@ std::string make_source(const DevConfig &dev, int num_sums, bool dense, const Ji
   // table: its template arguments are emitted here, not patched into the text afterwards
   std::ostringstream body_args;
   body_args << "true, " << (dense ? "true" : "false") << ", " << num_sums << ", " << jit_rows_per_thread();
-  if (geo.runs != 0 || geo.reg_groups != 0) {
+  if (geo.runs != 0 || geo.reg_groups != 0 || int_expr) {
     body_args << ", false, " << kABlock << ", false, " << (geo.runs != 0 ? "true" : "false");
-    if (geo.reg_groups != 0) body_args << ", " << geo.reg_groups;   // per-wave register accumulators (agg_hash_update.hpp, REG)
+    if (geo.reg_groups != 0 || int_expr) body_args << ", " << geo.reg_groups;   // per-wave register accumulators (agg_hash_update.hpp, REG)
+    if (int_expr) body_args << ", true";
   }
   o
     // explicit arguments are kept under 256 bytes (one view, the dictionaries behind a pointer): with the 256 hidden

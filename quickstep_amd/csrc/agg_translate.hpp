@@ -14,8 +14,8 @@ struct FinalizeDesc {
   int sum_col[QSX_MAX_AGGS];  // state column of the aggregate's accumulator (>= 1), 0 for COUNT(*)
   int nn_col[QSX_MAX_AGGS];   // state column counting the rows with a non-NULL argument (nullable arguments only), else -1:
                               // the row count stands for it
-  int is_int[QSX_MAX_AGGS];   // the accumulator word is a plain int64 (INT/LONG argument)
-  int val_type[QSX_MAX_AGGS]; // MIN/MAX: type of the output column (= the argument's; DOUBLE for expressions)
+  int is_int[QSX_MAX_AGGS];   // the accumulator word is a plain int64 (INT/LONG argument: a column or an integer temp)
+  int val_type[QSX_MAX_AGGS]; // MIN/MAX: type of the output column (= the argument's; DOUBLE for double expressions)
   int num_keys;
   int key_width[QSX_MAX_KEYS];
   int key_shift[QSX_MAX_KEYS];
@@ -59,6 +59,24 @@ constexpr bool valid_operand(const qsx_agg_config_t &c, const qsx_operand_t &o, 
     case QSX_OPD_CONST: return o.index >= 0 && o.index < QSX_MAX_CONSTS;
     case QSX_OPD_TEMP: return o.index >= 0 && o.index < QSX_MAX_TEMPS && ((defined_temps_mask >> o.index) & 1);
     default: return false;
+  }
+}
+
+// Type of an operand of an integer instruction (QSX_EX_IADD .. IDIV, include/qsx.h): QSX_INT, QSX_LONG, or -1 = not an
+// integer operand.  temp_type[t]: QSX_INT / QSX_LONG for a temp that an integer instruction produced, -1 for a double.
+constexpr int int_operand_type(const qsx_agg_config_t &c, const qsx_operand_t &o, const int (&temp_type)[QSX_MAX_TEMPS]) {
+  switch (o.kind) {
+    case QSX_OPD_COLUMN: {
+      const int t = c.column_type[o.index];
+      return t == QSX_INT || t == QSX_LONG ? t : -1;
+    }
+    case QSX_OPD_CONST: {
+      const double v = c.consts[o.index];
+      if (!(v >= -9007199254740992.0 && v <= 9007199254740992.0)) return -1;   // (NaN fails both)
+      if (static_cast<double>(static_cast<long long>(v)) != v) return -1;
+      return v >= -2147483648.0 && v <= 2147483647.0 ? QSX_INT : QSX_LONG;   // Scalar::IntLiteral's rule
+    }
+    default: return temp_type[o.index];
   }
 }
 
@@ -139,16 +157,32 @@ constexpr Translated translate(const qsx_agg_config_t &c) {
   d.wide_hash_mask = ~0ull;
   if (wide && (c.strategy == QSX_AGG_COLLISION_FREE || d.wide_words > kMaxKeyWords)) return fail(t, QSX_ERR_UNSUPPORTED);
   // expression program
+  // Every temp is typed: an integer instruction produces an INT (both operands INT) or a LONG, and reads integers only.  On
+  // the device an integer temp is operand kind kOpdIntTemp, and the op of an INT result carries kExNarrow: a compiled shape
+  // sees both as constants, and its text (agg_jit.hip) tells IADD from ADD.
   int defined = 0;
+  int temp_type[QSX_MAX_TEMPS] = {};
+  for (int k = 0; k < QSX_MAX_TEMPS; ++k) temp_type[k] = -1;
+  auto dev_operand = [&](const qsx_operand_t &o) constexpr -> DevOperand {
+    return DevOperand{o.kind == QSX_OPD_TEMP && temp_type[o.index] >= 0 ? kOpdIntTemp : o.kind, o.index};
+  };
   d.num_instrs = c.num_instrs;
   for (int k = 0; k < c.num_instrs; ++k) {
     const qsx_expr_instr_t &in = c.instrs[k];
-    if (in.op < QSX_EX_ADD || in.op > QSX_EX_DIV || in.dst < 0 || in.dst >= QSX_MAX_TEMPS) return fail(t, QSX_ERR_INVALID_ARGUMENT);
+    if (in.op < QSX_EX_ADD || in.op > QSX_EX_IDIV || in.dst < 0 || in.dst >= QSX_MAX_TEMPS) return fail(t, QSX_ERR_INVALID_ARGUMENT);
     if (!valid_operand(c, in.a, defined) || !valid_operand(c, in.b, defined)) return fail(t, QSX_ERR_INVALID_ARGUMENT);
     d.instrs[k].op = in.op;
     d.instrs[k].dst = in.dst;
-    d.instrs[k].a = DevOperand{in.a.kind, in.a.index};
-    d.instrs[k].b = DevOperand{in.b.kind, in.b.index};
+    d.instrs[k].a = dev_operand(in.a);
+    d.instrs[k].b = dev_operand(in.b);
+    int result_type = -1;
+    if (in.op >= QSX_EX_IADD) {
+      const int ta = int_operand_type(c, in.a, temp_type), tb = int_operand_type(c, in.b, temp_type);
+      if (ta < 0 || tb < 0) return fail(t, QSX_ERR_INVALID_ARGUMENT);   // no implicit double -> integer conversion
+      result_type = ta == QSX_INT && tb == QSX_INT ? QSX_INT : QSX_LONG;
+      if (result_type == QSX_INT) d.instrs[k].op |= kExNarrow;
+    }
+    temp_type[in.dst] = result_type;
     defined |= 1 << in.dst;
   }
   for (int k = 0; k < QSX_MAX_CONSTS; ++k) d.consts[k] = c.consts[k];
@@ -213,19 +247,22 @@ constexpr Translated translate(const qsx_agg_config_t &c) {
       continue;
     }
     if (ag.fn == QSX_AGG_AVG || ag.fn == QSX_AGG_MIN || ag.fn == QSX_AGG_MAX) needs_count = true;   // NULL over zero rows
-    const bool is_int = ag.arg.kind == QSX_OPD_COLUMN &&
-                        (c.column_type[ag.arg.index] == QSX_INT || c.column_type[ag.arg.index] == QSX_LONG);
+    // (a temp has the type of its latest definition)
+    const int arg_type = ag.arg.kind == QSX_OPD_COLUMN ? c.column_type[ag.arg.index]
+                                                       : (temp_type[ag.arg.index] >= 0 ? temp_type[ag.arg.index] : QSX_DOUBLE);
+    const bool is_int = arg_type == QSX_INT || arg_type == QSX_LONG;
+    const DevOperand dev_arg = dev_operand(ag.arg);
     f.is_int[a] = is_int ? 1 : 0;
-    f.val_type[a] = ag.arg.kind == QSX_OPD_COLUMN ? c.column_type[ag.arg.index] : QSX_DOUBLE;
+    f.val_type[a] = arg_type;
     const int kind = ag.fn == QSX_AGG_MIN ? kAccMinI64 : (ag.fn == QSX_AGG_MAX ? kAccMaxI64 : (is_int ? kAccSumI64 : kAccSumF64));
     // SUM(x) and AVG(x) over the same argument share one accumulator (what
     // ReuseAggregateExpressions does on the optimizer side,
     // query_optimizer/rules/ReuseAggregateExpressions.hpp:43-80); so do repeated MIN(x) / MAX(x).
     int j = 0;
-    while (j < ns && !(d.sums[j].count_valid == 0 && d.sums[j].arg.kind == ag.arg.kind && d.sums[j].arg.index == ag.arg.index && d.sums[j].kind == kind)) ++j;
+    while (j < ns && !(d.sums[j].count_valid == 0 && d.sums[j].arg.kind == dev_arg.kind && d.sums[j].arg.index == dev_arg.index && d.sums[j].kind == kind)) ++j;
     if (j == ns) {
       if (ns == kMaxSums) return fail(t, QSX_ERR_UNSUPPORTED);
-      d.sums[ns].arg = DevOperand{ag.arg.kind, ag.arg.index};
+      d.sums[ns].arg = dev_arg;
       d.sums[ns].is_int = is_int ? 1 : 0;
       d.sums[ns].kind = kind;
       d.sums[ns].null_mask = arg_nulls;

@@ -879,15 +879,21 @@ static const AggTuning &agg_tuning() {
 // Temps get slots by liveness: a value's slot is free again after its last reader, and the reader
 // itself may reuse it for its result (a thread reads its rows before it writes them).
 static void plan_interpreter(DevConfig &dc, int tile_rows) {
-  auto resolve = [&](const DevOperand &o, const int (&slot_of_temp)[QSX_MAX_TEMPS]) {
+  // (as_int: the operand of an integer instruction — translate() has checked that it is an integer)
+  auto resolve = [&](const DevOperand &o, const int (&slot_of_temp)[QSX_MAX_TEMPS], bool as_int) {
     PlanOperand p{};
     switch (o.kind) {
       case QSX_OPD_CONST:
-        p.mode = kPlanImm;
+        p.mode = as_int ? kPlanImmI64 : kPlanImm;
         p.imm = dc.consts[o.index];
+        if (as_int) {
+          const long long bits = static_cast<long long>(dc.consts[o.index]);
+          std::memcpy(&p.imm, &bits, sizeof(bits));
+        }
         break;
       case QSX_OPD_TEMP:
-        p.mode = kPlanTempF64;
+      case kOpdIntTemp:
+        p.mode = o.kind == kOpdIntTemp ? kPlanTempI64 : kPlanTempF64;
         p.off = slot_of_temp[o.index] * tile_rows * 8;
         break;
       default:
@@ -909,8 +915,8 @@ static void plan_interpreter(DevConfig &dc, int tile_rows) {
     last_use[k] = -1;
     const int temp = dc.instrs[k].dst;
     for (int j = k + 1; j < n; ++j) {
-      if ((dc.instrs[j].a.kind == QSX_OPD_TEMP && dc.instrs[j].a.index == temp) ||
-          (dc.instrs[j].b.kind == QSX_OPD_TEMP && dc.instrs[j].b.index == temp)) {
+      if ((is_temp_kind(dc.instrs[j].a.kind) && dc.instrs[j].a.index == temp) ||
+          (is_temp_kind(dc.instrs[j].b.kind) && dc.instrs[j].b.index == temp)) {
         last_use[k] = j;
       }
       if (dc.instrs[j].dst == temp) break;  // redefined: later readers see the new value
@@ -919,7 +925,7 @@ static void plan_interpreter(DevConfig &dc, int tile_rows) {
     for (int j = k + 1; j < n; ++j) redefined = redefined || dc.instrs[j].dst == temp;
     if (!redefined) {
       for (int j = 0; j < dc.num_sums; ++j) {
-        if (dc.sums[j].arg.kind == QSX_OPD_TEMP && dc.sums[j].arg.index == temp) last_use[k] = n;
+        if (is_temp_kind(dc.sums[j].arg.kind) && dc.sums[j].arg.index == temp) last_use[k] = n;
       }
     }
   }
@@ -930,8 +936,9 @@ static void plan_interpreter(DevConfig &dc, int tile_rows) {
   for (int k = 0; k < n; ++k) {
     PlanInstr &pi = dc.plan_instrs[k];
     pi.op = dc.instrs[k].op;
-    pi.a = resolve(dc.instrs[k].a, slot_of_temp);   // operands see the slots before this result is placed
-    pi.b = resolve(dc.instrs[k].b, slot_of_temp);
+    const bool as_int = pi.op >= QSX_EX_IADD;
+    pi.a = resolve(dc.instrs[k].a, slot_of_temp, as_int);   // operands see the slots before this result is placed
+    pi.b = resolve(dc.instrs[k].b, slot_of_temp, as_int);
     if (last_use[k] < 0) {
       pi.dst_off = -1;
       continue;
@@ -954,7 +961,7 @@ static void plan_interpreter(DevConfig &dc, int tile_rows) {
       ps.width = 8;
       continue;
     }
-    ps.arg = resolve(dc.sums[j].arg, slot_of_temp);
+    ps.arg = resolve(dc.sums[j].arg, slot_of_temp, false);
     ps.width = dc.sums[j].arg.kind == QSX_OPD_COLUMN ? dc.column_width[dc.sums[j].arg.index] : 8;
   }
 }
@@ -2210,6 +2217,19 @@ extern "C" int qsx_debug_agg_factored_plan(const qsx_agg_config_t *config, int32
   for (int j = 0; j < kMaxSums; ++j) out[4 + j] = j < t.num_sums ? f.sum_hist[j] : -1;
   return QSX_OK;
 }
+// Test hook (not part of include/qsx.h; needs no GPU): translate()'s status for a configuration and, per aggregate, the type
+// of its output column's values (FinalizeDesc::val_type; meaningful for SUM / AVG / MIN / MAX) and whether its accumulator
+// is an int64 (FinalizeDesc::is_int).
+extern "C" int qsx_debug_agg_translate(const qsx_agg_config_t *config, int32_t *out_val_types, int32_t *out_is_int, int cap) {
+  if (config == nullptr) return QSX_ERR_INVALID_ARGUMENT;
+  const Translated t = translate(*config);
+  if (t.status != QSX_OK) return t.status;
+  for (int a = 0; a < t.fin.num_aggs && a < cap; ++a) {
+    if (out_val_types != nullptr) out_val_types[a] = t.fin.val_type[a];
+    if (out_is_int != nullptr) out_is_int[a] = t.fin.is_int[a];
+  }
+  return QSX_OK;
+}
 static bool factored_enabled() {
   const char *e = getenv("QSX_AGG_FACTORED");
   return e == nullptr || e[0] != '0';
@@ -2545,9 +2565,19 @@ static bool two_level_plan(const qsx_agg_state *st) {
     return false;
   }
   if (d.num_keys < 1) return false;
+  // Integer temps come from the integer evaluator, double temps from the double one: a purely integer program or a purely
+  // double one.  A program that mixes the two stays on the one-pass path.
+  int int_instrs = 0;
+  for (int k = 0; k < d.num_instrs; ++k) int_instrs += d.instrs[k].op >= QSX_EX_IADD ? 1 : 0;
+  if (int_instrs != 0 && int_instrs != d.num_instrs) return false;
   for (int j = 0; j < st->num_sums; ++j) {
     const DevSum &sum = d.sums[j];
     if (sum.count_valid != 0 || sum.null_mask != 0) return false;
+    if (sum.arg.kind == kOpdIntTemp) {
+      // an integer expression: a stripe of INT / LONG values in front of the passes (update_two_level)
+      if (sum.is_int == 0 || sum.kind == kAccSumF64 || sum.arg.index < 0 || sum.arg.index >= QSX_MAX_TEMPS) return false;
+      continue;
+    }
     if (sum.arg.kind == QSX_OPD_TEMP) {
       // an expression (DOUBLE arithmetic): its values become a stripe in front of the passes (update_two_level)
       if (sum.is_int != 0 || sum.kind == kAccSumI64 || sum.arg.index < 0 || sum.arg.index >= QSX_MAX_TEMPS) return false;
@@ -2620,6 +2650,12 @@ static int update_two_level(qsx_agg_state *st, const void *const *cols, int64_t 
   int moved = 0, item_of_column[QSX_MAX_COLUMNS], item_of_temp[QSX_MAX_TEMPS], item_of_sum[kMaxSums];
   for (int &v : item_of_column) v = -1;
   for (int &v : item_of_temp) v = -1;
+  // type of an integer temp (kOpdIntTemp), -1 for a double one: that of its latest definition
+  int temp_type[QSX_MAX_TEMPS];
+  for (int &v : temp_type) v = -1;
+  for (int k = 0; k < d.num_instrs; ++k) {
+    temp_type[d.instrs[k].dst] = d.instrs[k].op < QSX_EX_IADD ? -1 : ((d.instrs[k].op & kExNarrow) != 0 ? QSX_INT : QSX_LONG);
+  }
   auto need_column = [&](int c) {
     if (item_of_column[c] < 0) {
       items[moved] = Moved{cols[c], d.column_width[c], nullptr, nullptr};
@@ -2633,9 +2669,9 @@ static int update_two_level(qsx_agg_state *st, const void *const *cols, int64_t 
     const DevOperand &arg = d.sums[j].arg;
     if (arg.kind == QSX_OPD_COLUMN) {
       item_of_sum[j] = need_column(arg.index);
-    } else {   // QSX_OPD_TEMP (two_level_plan)
+    } else {   // QSX_OPD_TEMP / kOpdIntTemp (two_level_plan)
       if (item_of_temp[arg.index] < 0) {
-        items[moved] = Moved{nullptr, 8, nullptr, nullptr};
+        items[moved] = Moved{nullptr, temp_type[arg.index] == QSX_INT ? 4 : 8, nullptr, nullptr};
         item_of_temp[arg.index] = moved++;
         ++num_temps;
       }
@@ -2664,13 +2700,29 @@ static int update_two_level(qsx_agg_state *st, const void *const *cols, int64_t 
       eval_cols[c] = numeric && cols[c] != nullptr ? cols[c] : any;
       eval_types[c] = numeric && cols[c] != nullptr ? type : QSX_INT;
     }
+    // (the integer evaluator takes INT / LONG stripes only: what a purely integer program never reads stands in as INT)
+    int32_t int_types[QSX_MAX_COLUMNS];
+    int64_t int_consts[QSX_MAX_CONSTS];
+    for (int c = 0; c < ncols; ++c) int_types[c] = eval_types[c] == QSX_LONG ? QSX_LONG : QSX_INT;
+    for (int k = 0; k < QSX_MAX_CONSTS; ++k) {
+      const double v = st->config.consts[k];
+      int_consts[k] = v >= -9007199254740992.0 && v <= 9007199254740992.0 ? static_cast<int64_t>(v) : 0;   // (unused unless integral)
+    }
     for (int t = 0; t < QSX_MAX_TEMPS; ++t) {
       if (item_of_temp[t] < 0) continue;
-      double *values = static_cast<double *>(scratch.take(static_cast<size_t>(n) * 8 + 16));
-      if (values == nullptr) return QSX_ERR_OUT_OF_MEMORY;
+      void *stripe = scratch.take(static_cast<size_t>(n) * 8 + 16);
+      if (stripe == nullptr) return QSX_ERR_OUT_OF_MEMORY;
+      double *values = static_cast<double *>(stripe);
       qsx_operand_t result{};
       result.kind = QSX_OPD_TEMP;
       result.index = t;
+      if (temp_type[t] >= 0) {
+        rc = qsx_eval_expression_long(ncols, eval_cols, int_types, st->config.num_instrs, st->config.instrs, int_consts, result, n,
+                                      temp_type[t] == QSX_INT ? 4 : 8, stripe, reinterpret_cast<qsx_stream_t>(s));
+        if (rc != QSX_OK) return rc;
+        items[item_of_temp[t]].src = stripe;
+        continue;
+      }
       rc = qsx_eval_expression(ncols, eval_cols, eval_types, st->config.num_instrs, st->config.instrs, st->config.consts, result, n, values,
                                reinterpret_cast<qsx_stream_t>(s));
       if (rc != QSX_OK) return rc;
@@ -2712,7 +2764,8 @@ static int update_two_level(qsx_agg_state *st, const void *const *cols, int64_t 
   a.num_sums = st->num_sums;
   for (int j = 0; j < st->num_sums; ++j) {
     a.sum_col[j] = items[item_of_sum[j]].second;
-    a.sum_type[j] = d.sums[j].arg.kind == QSX_OPD_COLUMN ? d.column_type[d.sums[j].arg.index] : QSX_DOUBLE;
+    a.sum_type[j] = d.sums[j].arg.kind == QSX_OPD_COLUMN ? d.column_type[d.sums[j].arg.index]
+                                                         : (d.sums[j].arg.kind == kOpdIntTemp ? temp_type[d.sums[j].arg.index] : QSX_DOUBLE);
     a.sum_kind[j] = d.sums[j].kind;
   }
   a.bounds = bounds;
@@ -3783,10 +3836,10 @@ int qsx_eval_expression_long(int num_columns, const void *const *cols, const int
   };
   for (int k = 0; k < num_instrs; ++k) {
     const qsx_expr_instr_t &in = instrs[k];
-    if (in.op < QSX_EX_ADD || in.op > QSX_EX_DIV || in.dst < 0 || in.dst >= QSX_MAX_TEMPS || !valid(in.a) || !valid(in.b)) {
+    if (in.op < QSX_EX_ADD || in.op > QSX_EX_IDIV || in.dst < 0 || in.dst >= QSX_MAX_TEMPS || !valid(in.a) || !valid(in.b)) {
       return QSX_ERR_INVALID_ARGUMENT;
     }
-    prog.instrs[k].op = in.op;
+    prog.instrs[k].op = in.op & 3;   // (QSX_EX_IADD .. IDIV: synonyms of the plain ops here)
     prog.instrs[k].dst = in.dst;
     prog.instrs[k].a = DevOperand{in.a.kind, in.a.index};
     prog.instrs[k].b = DevOperand{in.b.kind, in.b.index};

@@ -490,7 +490,8 @@ qsx_operand_t ExpressionFlattener::add(const ScalarPtr &scalar) {
     }
     default: {
       const qsx_operand_t a = add(scalar->left), b = add(scalar->right);
-      const std::int32_t op = static_cast<std::int32_t>(scalar->operation);   // kAdd .. kDivide = QSX_EX_ADD .. QSX_EX_DIV
+      std::int32_t op = static_cast<std::int32_t>(scalar->operation);   // kAdd .. kDivide = QSX_EX_ADD .. QSX_EX_DIV
+      if (integer_relation_ != nullptr && ScalarResultType(scalar, *integer_relation_) != kDouble) op += QSX_EX_IADD;   // .. IDIV
       for (const qsx_expr_instr_t &in : instrs_) {   // the same node again (shared subexpression): its temp
         if (in.op == op && in.a.kind == a.kind && in.a.index == a.index && in.b.kind == b.kind && in.b.index == b.index) {
           return qsx_operand_t{QSX_OPD_TEMP, in.dst};
@@ -533,7 +534,7 @@ AggregationOperationState::AggregationOperationState(const AggregationStateSpec 
   config_.num_keys = static_cast<int>(spec.group_by.size());
   for (std::size_t k = 0; k < spec.group_by.size(); ++k) config_.key_column[k] = column_of(spec.group_by[k]);
   int num_main = 0;
-  ExpressionFlattener flattener(column_of);
+  ExpressionFlattener flattener(column_of, spec.integer_argument_arithmetic ? &rel : nullptr);
   for (std::size_t a = 0; a < spec_.aggregates.size(); ++a) {
     if (spec_.aggregates[a].argument_expression != nullptr && spec_.aggregates[a].argument_expression->kind == Scalar::kAttribute) {
       spec_.aggregates[a].argument = spec_.aggregates[a].argument_expression->attribute;   // ScalarAttribute: the plain form
@@ -947,7 +948,13 @@ void AggregationOperationState::finalizeWithDistinct(InsertDestination *dest) {
     for (std::size_t a = 0; a < spec_.aggregates.size(); ++a) {
       if (main_agg_[a] < 0) continue;
       const AggregateSpec &ag = spec_.aggregates[a];
-      main_types.push_back(AggResultType(ag.function, ag.argument_expression != nullptr ? Type::Double()   // expressions evaluate in DOUBLE
+      Type expression_type = Type::Double();   // expressions evaluate in DOUBLE, but for integer-typed ones under the spec's flag
+      if (ag.argument_expression != nullptr && spec_.integer_argument_arithmetic) {
+        const TypeID id = ScalarResultType(ag.argument_expression, rel);
+        if (id == kInt) expression_type = Type::Int();
+        if (id == kLong) expression_type = Type::Long();
+      }
+      main_types.push_back(AggResultType(ag.function, ag.argument_expression != nullptr ? expression_type
                                                       : ag.argument == kInvalidAttributeID ? Type::Long() : rel.getAttributeType(ag.argument)));
     }
     finalize_into(state_, config_, main_types, &main);

@@ -448,8 +448,9 @@ class Scalar {
 };
 // The type of a Scalar over `relation` by the reference's rule for arithmetic (BinaryOperation::resultTypeForArgumentTypes,
 // types/operations/binary_operations/ArithmeticBinaryOperation.hpp): DOUBLE as soon as a FLOAT / DOUBLE is involved, else LONG
-// if a LONG is, else INT.  Integer-typed trees are evaluated in integer arithmetic (qsx_eval_expression_long) by the
-// SelectOperator's general form; aggregate arguments are evaluated in double inside the aggregation kernel (exact below 2^53).
+// if a LONG is, else INT.  Integer-typed trees are evaluated in integer arithmetic by the SelectOperator's general form
+// (qsx_eval_expression_long) and, when AggregationStateSpec::integer_argument_arithmetic is set, inside the aggregation kernel
+// (QSX_EX_IADD .. IDIV); without that flag aggregate arguments are evaluated in double (exact below 2^53) and typed DOUBLE.
 TypeID ScalarResultType(const ScalarPtr &scalar, const CatalogRelation &relation);
 // Scalar trees flattened into one expression program (qsx_expr_instr_t[]): one instruction per distinct binary node —
 // a subexpression shared by several scalars is computed once, the role of the reference's ColumnVectorCache — input
@@ -457,11 +458,17 @@ TypeID ScalarResultType(const ScalarPtr &scalar, const CatalogRelation &relation
 class ExpressionFlattener {
  public:
   explicit ExpressionFlattener(std::function<int(attribute_id)> column_of) : column_of_(std::move(column_of)) {}
+  // integer_relation != nullptr: a node whose own subtree has ScalarResultType INT / LONG over that relation becomes an
+  // integer instruction (QSX_EX_IADD .. IDIV) — also inside a DOUBLE-typed tree, which is what the reference computes for
+  // (a + b) * 0.5 with integer a, b.  Otherwise every node is a double instruction.
+  ExpressionFlattener(std::function<int(attribute_id)> column_of, const CatalogRelation *integer_relation)
+      : column_of_(std::move(column_of)), integer_relation_(integer_relation) {}
   qsx_operand_t add(const ScalarPtr &scalar);   // the operand holding the scalar's value
   const std::vector<qsx_expr_instr_t> &instrs() const { return instrs_; }
   const std::vector<double> &consts() const { return consts_; }
  private:
   std::function<int(attribute_id)> column_of_;
+  const CatalogRelation *integer_relation_ = nullptr;
   std::vector<qsx_expr_instr_t> instrs_;
   std::vector<double> consts_;
 };
@@ -488,6 +495,11 @@ struct AggregationStateSpec {
   qsx_agg_strategy_t strategy = QSX_AGG_GENERIC;
   std::int64_t estimated_num_groups = 16;
   std::int64_t collision_free_num_entries = 0;
+  // A non-DISTINCT aggregate whose argument_expression has ScalarResultType INT / LONG is evaluated in integer arithmetic
+  // (INT op INT wraps to 32 bits, anything with a LONG to 64: ArithmeticBinaryOperators.hpp:203-340) and its result
+  // attribute is the reference's: LONG for SUM, the expression's type for MIN / MAX, DOUBLE for AVG.  false (the default):
+  // such an argument is evaluated in double and the result attribute is DOUBLE.
+  bool integer_argument_arithmetic = false;
 };
 
 class AggregationOperationState {

@@ -22,6 +22,7 @@ AGG_COUNT_STAR, AGG_SUM, AGG_AVG, AGG_MIN, AGG_MAX, AGG_COUNT = range(6)
 OPD_COLUMN, OPD_CONST, OPD_TEMP = range(3)
 # qsx_expr_op_t
 EX_ADD, EX_SUB, EX_MUL, EX_DIV = range(4)
+EX_IADD, EX_ISUB, EX_IMUL, EX_IDIV = range(4, 8)                    # the same in integer arithmetic (include/qsx.h)
 # qsx_lip_kind_t
 LIP_SINGLE_IDENTITY_HASH, LIP_BITVECTOR_EXACT = range(2)
 
@@ -148,27 +149,60 @@ def make_agg_config(strategy, columns, keys=(), instrs=(), consts=(), aggs=(), p
     return cfg
 
 
+def int_operand_type(cfg, operand, temp_types):
+    """INT or LONG for an operand an integer instruction (EX_IADD .. EX_IDIV) accepts, else None: an INT / LONG column, a temp
+    of an integer instruction, an integral constant with |c| <= 2^53 (INT when it fits 32 bits)."""
+    if operand.kind == OPD_COLUMN:
+        t = cfg.column_type[operand.index]
+        return t if t in (INT, LONG) else None
+    if operand.kind == OPD_CONST:
+        v = cfg.consts[operand.index]
+        if not (-2.0 ** 53 <= v <= 2.0 ** 53) or v != int(v):
+            return None
+        return INT if -2 ** 31 <= int(v) < 2 ** 31 else LONG
+    return temp_types.get(operand.index)
+
+
+def temp_types(cfg):
+    """{temp: INT | LONG | None (a double)} after the whole program: a temp has the type of its latest definition."""
+    types = {}
+    for k in range(cfg.num_instrs):
+        ins = cfg.instrs[k]
+        if ins.op >= EX_IADD:
+            ta, tb = int_operand_type(cfg, ins.a, types), int_operand_type(cfg, ins.b, types)
+            types[ins.dst] = None if ta is None or tb is None else (INT if ta == INT and tb == INT else LONG)
+        else:
+            types[ins.dst] = None
+    return types
+
+
+def agg_argument_type(cfg, a):
+    """Type of aggregate `a`'s argument: the column's, INT / LONG for an integer temp, DOUBLE for a double temp."""
+    arg = cfg.aggs[a].arg
+    if arg.kind == OPD_COLUMN:
+        return cfg.column_type[arg.index]
+    t = temp_types(cfg).get(arg.index)
+    return DOUBLE if t is None else t
+
+
 def agg_output_dtype(cfg, a):
     """numpy dtype name of the value column qsx_agg_finalize writes for aggregate `a`: int64 for COUNT
-    and SUM over INT/LONG, float64 for the other SUMs and AVG, the argument's own type for MIN/MAX."""
+    and SUM over INT/LONG (a column or an integer expression), float64 for the other SUMs and AVG, the argument's own type
+    for MIN/MAX."""
     fn = cfg.aggs[a].fn
     if fn in (AGG_MIN, AGG_MAX):
-        arg = cfg.aggs[a].arg
-        if arg.kind != OPD_COLUMN:
-            return "float64"
-        return {INT: "int32", LONG: "int64", FLOAT: "float32", DOUBLE: "float64"}[cfg.column_type[arg.index]]
+        return {INT: "int32", LONG: "int64", FLOAT: "float32", DOUBLE: "float64"}[agg_argument_type(cfg, a)]
     return "int64" if agg_output_is_int(cfg, a) else "float64"
 
 
 def agg_output_is_int(cfg, a):
-    """True when aggregate `a` finalizes to int64 (COUNT, SUM over INT/LONG)."""
+    """True when aggregate `a` finalizes to int64 (COUNT, SUM over INT/LONG: a column or an integer expression)."""
     fn = cfg.aggs[a].fn
     if fn in (AGG_COUNT_STAR, AGG_COUNT):
         return True
     if fn == AGG_AVG:
         return False
-    arg = cfg.aggs[a].arg
-    return arg.kind == OPD_COLUMN and cfg.column_type[arg.index] in (INT, LONG)
+    return agg_argument_type(cfg, a) in (INT, LONG)
 
 
 MAX_PROJECTED = 16                                                  # QSX_MAX_PROJECTED

@@ -1049,6 +1049,48 @@ int qsx_sort_top_k(int nkeys, const void *const *key_cols, const int32_t *key_ty
                    const int32_t *descending, int64_t n, int64_t k, int32_t *out_tids_dev,
                    void *workspace_dev, size_t workspace_bytes, qsx_stream_t stream);
 
+/* ORDER BY with NULLS FIRST / LAST and CHAR(n) keys.  One descriptor per ORDER BY column; the two functions below are
+ * qsx_sort_permutation / qsx_sort_top_k over such descriptors (QSX_ABI_VERSION did not change: a caller detects the
+ * capability by the presence of the symbols).
+ *
+ * Key order: key 0 is most significant; the order is that of StorageBlock::sort (storage/StorageBlock.cpp:561-601): one
+ * stable pass per ORDER BY column from the last to the first (comparator chain of utility/SortConfiguration.hpp:51-130,
+ * which carries `null_first` per column).
+ * NULLs: within one key the rows that are NULL in it come before all its non-NULL rows (nulls_first != 0) or after them,
+ * whatever `descending` says (StorageBlock::sortColumn, storage/StorageBlock.cpp:603-689: the NULL rows are set aside and
+ * put in front or behind at :679-688).  Among themselves the NULL rows keep the order the less significant keys gave
+ * them, then input order.  The bytes under a NULL are never looked at.
+ * Non-NULL rows are ordered as by qsx_sort_permutation: ASC or DESC, ties keep the input order in both directions,
+ * -0.0 == +0.0.  NaN is outside the contract (as there).
+ * QSX_CHAR of width w (1..64): the comparison qsx_select_cmp_char documents (types/operations/comparisons/
+ * AsciiStringComparators.hpp:218-251): a value ends at its first NUL byte or at w, bytes compare as unsigned chars, a
+ * proper prefix is smaller, the bytes behind the first NUL are ignored.
+ * Refused: a CHAR width outside 1..64 or a type outside the list -> QSX_ERR_UNSUPPORTED; a NULL col_dev with n > 0,
+ * nkeys outside 1..QSX_MAX_KEYS, or a width other than 0 / the natural one on a non-CHAR key -> QSX_ERR_INVALID_ARGUMENT;
+ * no device -> QSX_ERR_NO_DEVICE.
+ * With NULL-free INT / LONG / FLOAT / DOUBLE / DATE / CHAR(1) keys the result equals qsx_sort_permutation's exactly;
+ * qsx_sort_top_k_keys returns exactly the first min(k, n) entries of qsx_sort_permutation_keys.
+ * Workspace = qsx_sort_workspace_bytes(n) for both (one buffer serves both families).
+ * Both calls synchronise the stream once: a first kernel reads every key once and reports which bits of the keys' 64-bit
+ * images vary at all, and the host leaves out every radix digit (and every 8-byte word of a CHAR key) that does not —
+ * ASCII text never sets bit 7, CHAR(25) names are mostly padding in their last words, small integers leave their high
+ * digits constant.  qsx_sort_top_k_keys selects candidates by threshold like qsx_sort_top_k (and waits like it) when key 0
+ * is an INT / LONG / FLOAT / DOUBLE / DATE key without a null bitmap; with any other key 0 it sorts all rows. */
+typedef struct qsx_sort_key {
+  const void     *col_dev;          /* n values */
+  const uint64_t *null_bitmap_dev;  /* TupleIdSequence bit order, bit i set = row i is NULL; NULL pointer = no NULLs */
+  int32_t type;                     /* QSX_INT / LONG / FLOAT / DOUBLE / DATE / CHAR */
+  int32_t width;                    /* QSX_CHAR: bytes per value, 1..64; other types: 0 or the natural width */
+  int32_t descending;               /* != 0: DESC */
+  int32_t nulls_first;              /* != 0: NULL rows in front of the non-NULL rows of this key, else behind them */
+} qsx_sort_key_t;
+
+size_t qsx_abi_sizeof_sort_key(void);
+int qsx_sort_permutation_keys(int nkeys, const qsx_sort_key_t *keys, int64_t n, int32_t *out_tids_dev,
+                              void *workspace_dev, size_t workspace_bytes, qsx_stream_t stream);
+int qsx_sort_top_k_keys(int nkeys, const qsx_sort_key_t *keys, int64_t n, int64_t k, int32_t *out_tids_dev,
+                        void *workspace_dev, size_t workspace_bytes, qsx_stream_t stream);
+
 /* Distinctify: out_tids = row number of the first occurrence of every distinct tuple over ncols columns
  * (QSX_INT / LONG / FLOAT / DOUBLE, or 1-byte QSX_CHAR; at most QSX_MAX_KEYS), restricted to the rows of
  * filter_dev when non-NULL, listed in tuple order; *out_count_dev = number of distinct tuples.

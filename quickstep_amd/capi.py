@@ -85,6 +85,9 @@ _SIGNATURES = {
     "qsx_sort_permutation": (_int, [_int, _pp, C.POINTER(_i32), C.POINTER(_i32), _i64, _vp, _vp, _sz, _vp]),
     "qsx_distinct_rows": (_int, [_int, _pp, C.POINTER(_i32), _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "qsx_sort_top_k": (_int, [_int, _pp, C.POINTER(_i32), C.POINTER(_i32), _i64, _i64, _vp, _vp, _sz, _vp]),
+    "qsx_abi_sizeof_sort_key": (_sz, []),
+    "qsx_sort_permutation_keys": (_int, [_int, C.POINTER(T.SortKey), _i64, _vp, _vp, _sz, _vp]),
+    "qsx_sort_top_k_keys": (_int, [_int, C.POINTER(T.SortKey), _i64, _i64, _vp, _vp, _sz, _vp]),
     "qsx_join_table_create": (_int, [_int, _i64, _pp]),
     "qsx_join_table_create_dense": (_int, [_int, _i64, _i64, _i64, _i64, _pp]),
     "qsx_join_table_destroy": (_int, [_vp]),
@@ -177,6 +180,9 @@ for _name, (_res, _args) in _SIGNATURES.items():
 
 if _lib.qsx_abi_sizeof_agg_config() != C.sizeof(T.AggConfig):
     raise ImportError("quickstep_amd.types.AggConfig does not match qsx_agg_config_t of libqsx.so")
+
+if _lib.qsx_abi_sizeof_sort_key() != C.sizeof(T.SortKey):
+    raise ImportError("quickstep_amd.types.SortKey does not match qsx_sort_key_t of libqsx.so")
 
 lib = _lib
 EXPORTED = tuple(_SIGNATURES)
@@ -616,6 +622,57 @@ def sort_top_k(key_cols, k, descending=None, stream=None, types=None):
     desc = (C.c_int32 * len(key_cols))(*[1 if (descending and descending[i]) else 0 for i in range(len(key_cols))])
     _check(_lib.qsx_sort_top_k(len(key_cols), ptrs, types, desc, n, k, _ptr(out), _ptr(ws), ws_bytes, _stream(stream)),
            "qsx_sort_top_k")
+    return out[:k]
+
+
+class SortKeySpec:
+    """One ORDER BY column of sort_permutation_keys / sort_top_k_keys: `column` is a tensor of n values (CHAR(w): uint8,
+    n x w bytes), `null_bitmap` an int64 tensor of (n + 63) // 64 TupleIdSequence words (bit set = NULL) or None."""
+
+    def __init__(self, column, type=None, width=0, descending=False, nulls_first=False, null_bitmap=None):
+        self.column, self.width, self.null_bitmap = column, int(width), null_bitmap
+        self.type = qsx_type_of(column) if type is None else type
+        self.descending, self.nulls_first = bool(descending), bool(nulls_first)
+        if self.type == T.CHAR and self.width == 0:
+            self.width = 1
+
+    def rows(self):
+        return self.column.numel() // self.width if self.type == T.CHAR else self.column.numel()
+
+
+def _sort_keys(keys):
+    specs = [k if isinstance(k, SortKeySpec) else SortKeySpec(*k) for k in keys]
+    arr = (T.SortKey * max(len(specs), 1))()
+    for i, k in enumerate(specs):
+        arr[i] = T.SortKey(k.column.data_ptr(), None if k.null_bitmap is None else k.null_bitmap.data_ptr(), k.type, k.width,
+                           int(k.descending), int(k.nulls_first))
+    return specs, arr
+
+
+def sort_permutation_keys(keys, stream=None):
+    """ORDER BY with NULLS FIRST / LAST and CHAR(n) keys (qsx_sort_permutation_keys): `keys` is a list of SortKeySpec, or of
+    (column, type, width, descending, nulls_first, null_bitmap) records; int32 row numbers in output order (stable)."""
+    specs, arr = _sort_keys(keys)
+    n = specs[0].rows()
+    device = specs[0].column.device
+    out = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+    ws_bytes = _lib.qsx_sort_workspace_bytes(n)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=device)
+    _check(_lib.qsx_sort_permutation_keys(len(specs), arr, n, _ptr(out), _ptr(ws), ws_bytes, _stream(stream)),
+           "qsx_sort_permutation_keys")
+    return out[:n]
+
+
+def sort_top_k_keys(keys, k, stream=None):
+    """ORDER BY ... LIMIT k over the same keys -> the first min(k, n) row numbers of sort_permutation_keys' output."""
+    specs, arr = _sort_keys(keys)
+    n = specs[0].rows()
+    k = min(int(k), n)
+    device = specs[0].column.device
+    out = torch.empty(max(k, 1), dtype=torch.int32, device=device)
+    ws_bytes = _lib.qsx_sort_workspace_bytes(n)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=device)
+    _check(_lib.qsx_sort_top_k_keys(len(specs), arr, n, k, _ptr(out), _ptr(ws), ws_bytes, _stream(stream)), "qsx_sort_top_k_keys")
     return out[:k]
 
 

@@ -249,28 +249,109 @@ void SortBlocksInto(const std::vector<BlockReference> &blocks, const CatalogRela
     }
     stripes[a] = owned.back()->ptr;
   }
-  std::vector<const void *> key_cols;
-  std::vector<std::int32_t> key_types, descending;
+  // the blocks that hold rows, as segments of the concatenation (two segments must not start at the same row)
+  std::vector<const StorageBlock *> segment_blocks;
+  std::vector<std::int64_t> segment_first_row;
+  std::int64_t first_row = 0;
+  for (const BlockReference &b : blocks) {
+    if (b->numTuples() == 0) continue;
+    segment_blocks.push_back(b.get());
+    segment_first_row.push_back(first_row);
+    first_row += b->numTuples();
+  }
+  // bit i of dst = the null bit of attribute a in row tids[i] of the concatenation; false when no block has a bitmap for it
+  auto gather_nulls = [&](attribute_id a, const std::int32_t *tids, std::int64_t rows, std::uint64_t *dst) {
+    std::vector<const std::uint64_t *> segs;
+    bool any = false;
+    for (const StorageBlock *b : segment_blocks) {
+      segs.push_back(b->nullBitmap(a));
+      any = any || segs.back() != nullptr;
+    }
+    if (!any) return false;
+    CheckStatus(qsx_bitmap_gather_segmented(static_cast<int>(segs.size()), segs.data(), segment_first_row.data(), tids, rows, dst,
+                                            CurrentStream()), "qsx_bitmap_gather_segmented");
+    return true;
+  };
+  // The keys.  A nullable ORDER BY attribute is ordered with its null bitmap (NULLS FIRST / LAST as config.null_ordering
+  // says, StorageBlock::sortColumn), a CHAR attribute with its width: both need the *_keys entry points; the plain cases
+  // keep calling the plain ones.
+  std::vector<qsx_sort_key_t> keys;
+  std::vector<std::unique_ptr<DeviceBuffer>> key_bitmaps;
+  std::unique_ptr<DeviceBuffer> input_order;   // 0, 1, ..., n - 1 (multi-block inputs with a nullable key)
+  bool keyed = false;
   for (std::size_t k = 0; k < config.order_by.size(); ++k) {
-    key_cols.push_back(stripes.at(config.order_by[k]));
-    key_types.push_back(relation.getAttributeType(config.order_by[k]).id);
-    descending.push_back(config.ordering.at(k) ? 0 : 1);
+    const attribute_id a = config.order_by[k];
+    const Type &type = relation.getAttributeType(a);
+    qsx_sort_key_t key{};
+    key.col_dev = stripes.at(a);
+    key.type = type.id;
+    key.width = type.id == kChar ? type.width : 0;
+    key.descending = config.ordering.at(k) ? 0 : 1;
+    key.nulls_first = k < config.null_ordering.size() && config.null_ordering[k] ? 1 : 0;
+    if (type.nullable) {
+      if (segment_blocks.size() == 1) {
+        key.null_bitmap_dev = segment_blocks.front()->nullBitmap(a);   // a single block is used in place
+      } else {
+        // blocks end at arbitrary row counts: their bitmaps cannot be appended word-wise
+        if (input_order == nullptr) {
+          const std::size_t words = static_cast<std::size_t>((n + 63) / 64);
+          input_order.reset(new DeviceBuffer(static_cast<std::size_t>(n) * 4 + 16));
+          // the tuple ids of an all-ones TupleIdSequence; the temporaries live in `owned` until the function's final wait
+          const std::size_t tws = qsx_compact_workspace_bytes(n);
+          owned.emplace_back(new DeviceBuffer(words * 8));
+          std::uint64_t *zero = static_cast<std::uint64_t *>(owned.back()->ptr);
+          owned.emplace_back(new DeviceBuffer(words * 8));
+          std::uint64_t *ones = static_cast<std::uint64_t *>(owned.back()->ptr);
+          owned.emplace_back(new DeviceBuffer(tws + 256));
+          char *tw = static_cast<char *>(owned.back()->ptr);   // [count, padding to 256 bytes, compaction workspace]
+          CheckStatus(qsx_memset_device(zero, 0, words * 8, CurrentStream()), "qsx_memset_device");
+          CheckStatus(qsx_bitmap_combine(3, zero, nullptr, n, ones, CurrentStream()), "qsx_bitmap_combine");
+          CheckStatus(qsx_bitmap_to_tids(ones, n, 0, static_cast<std::int32_t *>(input_order->ptr), reinterpret_cast<std::int64_t *>(tw), tw + 256,
+                                         tws, CurrentStream()), "qsx_bitmap_to_tids");
+        }
+        key_bitmaps.emplace_back(new DeviceBuffer(static_cast<std::size_t>((n + 63) / 64 + 1) * 8));
+        if (gather_nulls(a, static_cast<const std::int32_t *>(input_order->ptr), n, static_cast<std::uint64_t *>(key_bitmaps.back()->ptr))) {
+          key.null_bitmap_dev = static_cast<const std::uint64_t *>(key_bitmaps.back()->ptr);
+        }
+      }
+    }
+    keyed = keyed || key.null_bitmap_dev != nullptr || (type.id == kChar && type.width > 1);
+    keys.push_back(key);
   }
   const std::size_t ws_bytes = qsx_sort_workspace_bytes(n);
   DeviceBuffer ws(ws_bytes), tids(static_cast<std::size_t>(n) * 4 + 16);
-  if (out_rows < n) {   // top_k: only the leading rows are wanted
-    CheckStatus(qsx_sort_top_k(static_cast<int>(key_cols.size()), key_cols.data(), key_types.data(), descending.data(), n, out_rows,
-                               static_cast<std::int32_t *>(tids.ptr), ws.ptr, ws_bytes, CurrentStream()),
-                "qsx_sort_top_k");
+  std::int32_t *order = static_cast<std::int32_t *>(tids.ptr);
+  if (keyed) {
+    if (out_rows < n) {
+      CheckStatus(qsx_sort_top_k_keys(static_cast<int>(keys.size()), keys.data(), n, out_rows, order, ws.ptr, ws_bytes, CurrentStream()),
+                  "qsx_sort_top_k_keys");
+    } else {
+      CheckStatus(qsx_sort_permutation_keys(static_cast<int>(keys.size()), keys.data(), n, order, ws.ptr, ws_bytes, CurrentStream()),
+                  "qsx_sort_permutation_keys");
+    }
   } else {
-    CheckStatus(qsx_sort_permutation(static_cast<int>(key_cols.size()), key_cols.data(), key_types.data(), descending.data(), n,
-                                     static_cast<std::int32_t *>(tids.ptr), ws.ptr, ws_bytes, CurrentStream()),
-                "qsx_sort_permutation");
+    std::vector<const void *> key_cols;
+    std::vector<std::int32_t> key_types, descending;
+    for (const qsx_sort_key_t &key : keys) {
+      key_cols.push_back(key.col_dev);
+      key_types.push_back(key.type);
+      descending.push_back(key.descending);
+    }
+    if (out_rows < n) {   // top_k: only the leading rows are wanted
+      CheckStatus(qsx_sort_top_k(static_cast<int>(key_cols.size()), key_cols.data(), key_types.data(), descending.data(), n, out_rows, order,
+                                 ws.ptr, ws_bytes, CurrentStream()), "qsx_sort_top_k");
+    } else {
+      CheckStatus(qsx_sort_permutation(static_cast<int>(key_cols.size()), key_cols.data(), key_types.data(), descending.data(), n, order,
+                                       ws.ptr, ws_bytes, CurrentStream()), "qsx_sort_permutation");
+    }
   }
   for (std::size_t a = 0; a < relation.size(); ++a) {
-    CheckStatus(qsx_gather(relation.getAttributeType(static_cast<attribute_id>(a)).width, stripes[a],
-                           static_cast<const std::int32_t *>(tids.ptr), out_rows, out->stripe(static_cast<attribute_id>(a)),
-                           CurrentStream()), "qsx_gather");
+    const Type &type = relation.getAttributeType(static_cast<attribute_id>(a));
+    CheckStatus(qsx_gather(type.width, stripes[a], order, out_rows, out->stripe(static_cast<attribute_id>(a)), CurrentStream()), "qsx_gather");
+    // the null bits of every nullable attribute travel with its values (the output block's bitmaps are zeroed at creation)
+    if (type.nullable && out->nullBitmap(static_cast<attribute_id>(a)) != nullptr) {
+      gather_nulls(static_cast<attribute_id>(a), order, out_rows, out->nullBitmap(static_cast<attribute_id>(a)));
+    }
   }
   CheckStatus(qsx_stream_synchronize(CurrentStream()), "qsx_stream_synchronize");
   dest->returnBlock(out_id, out_rows);

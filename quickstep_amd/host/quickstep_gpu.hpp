@@ -592,11 +592,13 @@ class QueryContext {
   // (the condition of query_optimizer/rules/InjectJoinFilters.cpp:130-150) -> the directly addressed table
   // flavour (qsx_join_table_create_dense); nullptr -> the hashed table.
   struct ExactKeyRange { std::int64_t min_value, max_value; };
-  // utility/SortConfiguration.hpp:51-130: ORDER BY attributes, ordering[i] true = ascending (no NULL inputs here, so
-  // the null_ordering vector of the reference has nothing to order)
+  // utility/SortConfiguration.hpp:51-130: ORDER BY attributes, ordering[i] true = ascending, null_ordering[i] true = the
+  // NULLs of attribute i come first (whatever the direction, StorageBlock.cpp:679-688).  An empty null_ordering means
+  // "all last".
   struct SortConfiguration {
     std::vector<attribute_id> order_by;
     std::vector<bool> ordering;
+    std::vector<bool> null_ordering = {};
   };
   typedef std::uint32_t sort_config_id;
   sort_config_id addSortConfig(SortConfiguration config) {

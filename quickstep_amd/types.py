@@ -213,3 +213,8 @@ class JoinProjection(C.Structure):                                   # qsx_join_
                 ("probe_stripes", C.POINTER(C.c_void_p)), ("num_build_segments", C.c_int32),
                 ("build_first_tids", C.POINTER(C.c_int64)), ("build_stripes", C.POINTER(C.c_void_p)),
                 ("out_columns", C.POINTER(C.c_void_p))]
+
+
+class SortKey(C.Structure):                                          # qsx_sort_key_t
+    _fields_ = [("col_dev", C.c_void_p), ("null_bitmap_dev", C.c_void_p), ("type", C.c_int32), ("width", C.c_int32),
+                ("descending", C.c_int32), ("nulls_first", C.c_int32)]

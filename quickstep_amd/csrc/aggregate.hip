@@ -35,6 +35,7 @@
 #include "agg_hash_update.hpp"
 #include "agg_factored.hpp"
 #include "agg_shapes.hpp"
+#include "agg_stream.hpp"
 #include "agg_family.hpp"
 #include "agg_pieces.hpp"
 #include "agg_jit.hpp"
@@ -1221,6 +1222,10 @@ static int launch_dir(DevConfig dc, unsigned used_columns, int64_t n, const uint
   return QSX_OK;
 }
 
+static std::atomic<long long> g_stream_launches{0};
+// Test hook (not part of include/qsx.h): update calls this process has issued through the stream kernel (agg_stream.hpp).
+extern "C" long long qsx_debug_agg_stream_launches(void) { return g_stream_launches.load(std::memory_order_relaxed); }
+
 template <typename Shape, int V>
 static int launch_shape_v(const void *const *cols, int num_columns, int64_t n, const HashTableView &g, int S,
                           int ranges, const long long *pieces, hipStream_t stream, bool runs) {
@@ -1300,6 +1305,14 @@ static int launch_shape_v(const void *const *cols, int num_columns, int64_t n, c
     return QSX_OK;
   }
   if (nbuf == 1 && S == 16 && rep_shift == 4 && ranges == 1 && pieces == nullptr) {
+    // a handful of groups over plain, aligned columns: rows stream through registers, no LDS tile (agg_stream.hpp)
+    if constexpr (stream_serves(T)) {
+      if (!reg_groups_enabled() && agg_stream_enabled() && AggStream<Shape>::takes(cols, num_columns, n)) {
+        const int stream_rc = AggStream<Shape>::launch(cols, num_columns, n, g, stream);
+        if (stream_rc == QSX_OK) g_stream_launches.fetch_add(1, std::memory_order_relaxed);
+        return stream_rc;
+      }
+    }
     if (reg_groups_enabled()) QSX_LAUNCH_FIXED(16, 4, 1, true);
     QSX_LAUNCH_FIXED(16, 4, 1, false);
   }

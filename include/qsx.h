@@ -180,6 +180,35 @@ int qsx_select_cmp_char_blocks(int width, int64_t num_blocks, const int64_t *blo
                                const void *literal, int literal_length, const uint64_t *const *block_filters,
                                uint64_t *const *block_out_bitmaps, int64_t *out_counts_dev, qsx_stream_t stream);
 
+/* K1 with LIKE / NOT LIKE on a CHAR(width) attribute: out_bitmap[i] = (match(col[i], pattern) XOR negate) [AND filter[i]].
+ * Replaces the scan loops of PatternMatchingUncheckedComparator (types/operations/comparisons/
+ * PatternMatchingComparators-inl.hpp:190-268: the pattern compiled once, matched against every value of the accessor;
+ * PatternMatchingComparison.cpp, ComparisonID::kLike / kNotLike) as reached from the getMatchesForPredicate loop that
+ * qsx_select_cmp_char replaces.
+ *   The text is the field's bytes up to its first NUL, or `width` bytes (PatternMatchingComparators.hpp:72-78); bytes behind
+ *   the terminator never take part.  The pattern likewise ends at its first NUL or at pattern_length (0..64).
+ *   '%' matches any run of bytes (the empty run and '\n' included), '_' exactly one byte, every other byte itself.  There is
+ *   NO escape character: a backslash is a literal backslash (transformLikeToRegex, PatternMatchingComparators.hpp:207-232).
+ *   The match is anchored at both ends (RE2::FullMatch).
+ *   Deviation: the reference's re2 runs in UTF-8 mode, so its '_' consumes a code point; CHAR comparisons of this library
+ *   are byte-wise (the AsciiString* comparators), so '_' is one BYTE here.  Parity is claimed for text of bytes < 0x80.
+ *   negate       0: LIKE, 1: NOT LIKE.  Bits at positions >= n of the last word are zero, also under negate.  NULLs are the
+ *                caller's (a NULL matches neither, PatternMatchingComparators.hpp:67-70: AND-NOT the null bitmap).
+ * Other arguments as qsx_select_cmp_char; out_count is overwritten.  width outside 1..255, negative lengths, negate not 0 / 1
+ * or NULL pointers with n > 0: QSX_ERR_INVALID_ARGUMENT; pattern_length > QSX_MAX_LIKE_PATTERN: QSX_ERR_UNSUPPORTED.
+ * Over a dictionary stripe (col_dev = dictionary, width = value_width, n = num_codes) the result is that dictionary's code
+ * set for qsx_select_codes_in_set.  (TPC-H: p_type LIKE 'PROMO%', p_name LIKE '%green%', o_comment NOT LIKE
+ * '%special%requests%'.)  QSX_ABI_VERSION did not change: a caller detects the capability by the presence of the symbols. */
+#define QSX_MAX_LIKE_PATTERN 64
+int qsx_select_like(const void *col_dev, int width, int64_t n, const void *pattern, int pattern_length, int negate,
+                    const uint64_t *filter_dev, uint64_t *out_bitmap_dev, int64_t *out_count_dev, qsx_stream_t stream);
+
+/* qsx_select_like over a run of blocks in one launch (arguments as qsx_select_cmp_char_blocks / qsx_select_like): the same
+ * PatternMatchingComparators-inl.hpp:190-268 loop, one SelectWorkOrder per block in the reference. */
+int qsx_select_like_blocks(int width, int64_t num_blocks, const int64_t *block_rows, const void *const *block_cols,
+                           const void *pattern, int pattern_length, int negate, const uint64_t *const *block_filters,
+                           uint64_t *const *block_out_bitmaps, int64_t *out_counts_dev, qsx_stream_t stream);
+
 /* qsx_select_cmp on the SORT COLUMN of a sorted column store (ascending, no NULLs in the first n rows): the matches are
  * one row range found by two searches, not a scan.  Replaces SortColumnPredicateEvaluator::
  * EvaluatePredicateForUncompressedSortColumn (storage/ColumnStoreUtil.cpp:40-280) as called from
@@ -244,6 +273,25 @@ int qsx_select_codes_blocks(int code_width, int64_t num_blocks, const int64_t *b
                             const int32_t *block_ops, const uint32_t *block_first, const uint32_t *block_second,
                             const uint64_t *const *block_filters, uint64_t *const *block_out_bitmaps, int64_t *out_counts_dev,
                             qsx_stream_t stream);
+
+/* K1 on a code stripe against a SET of codes: out_bitmap[i] = set[codes[i]] [AND filter[i]], 0 for codes[i] >= num_codes.
+ * The reference has no code-set scan: a LIKE on a compressed attribute decompresses every value and runs the matcher on it
+ * (PatternMatchingComparators-inl.hpp:190-268 over the CompressedColumnStoreValueAccessor); here the pattern is matched
+ * against the block's dictionary once (qsx_select_like over the dictionary stripe) and the rows only test membership.
+ *   code_width   1, 2 or 4 (else QSX_ERR_UNSUPPORTED)
+ *   set_dev      bitmap of num_codes bits in the layout of every qsx bitmap (a TupleIdSequence: bit i = bit 63 - i % 64 of
+ *                word i / 64), (num_codes + 63) / 64 words.  The reference's NULL code (= num_codes) is never in a set.
+ * filter / out_bitmap / out_count as in qsx_select_codes. */
+int qsx_select_codes_in_set(int code_width, const void *codes_dev, int64_t n, const uint64_t *set_dev, int64_t num_codes,
+                            const uint64_t *filter_dev, uint64_t *out_bitmap_dev, int64_t *out_count_dev, qsx_stream_t stream);
+
+/* qsx_select_codes_in_set over a run of blocks in one launch, one set and one num_codes per block (the dictionaries differ
+ * from block to block: CompressedTupleStorageSubBlock::getMatchesForPredicate, storage/CompressedTupleStorageSubBlock.cpp:
+ * 160-250, runs per block), one code width for the run.  block_sets / block_num_codes: host arrays. */
+int qsx_select_codes_in_set_blocks(int code_width, int64_t num_blocks, const int64_t *block_rows, const void *const *block_codes,
+                                   const uint64_t *const *block_sets, const int64_t *block_num_codes,
+                                   const uint64_t *const *block_filters, uint64_t *const *block_out_bitmaps,
+                                   int64_t *out_counts_dev, qsx_stream_t stream);
 
 /* K1 on the sort column of sorted column-store blocks, over a run of blocks in one launch: every block is sorted on its
  * own, so every block's matches are its own row range (one wave per block searches the bounds, then the bitmaps of the run

@@ -65,7 +65,9 @@ _SIGNATURES = {
     "qsx_select_cmp_sorted": (_int, [_int, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp]),
     "qsx_select_cmp_char": (_int, [_vp, _int, _i64, _int, C.c_char_p, _int, _vp, _vp, _vp, _vp]),
     "qsx_select_cmp_columns": (_int, [_int, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp]),
+    "qsx_select_like": (_int, [_vp, _int, _i64, C.c_char_p, _int, _int, _vp, _vp, _vp, _vp]),
     "qsx_select_codes": (_int, [_int, _vp, _i64, _int, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "qsx_select_codes_in_set": (_int, [_int, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "qsx_select_codes_sorted": (_int, [_int, _vp, _i64, _int, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
     "qsx_decode_codes": (_int, [_int, _vp, _i64, _vp, _int, _vp, _vp]),
     "qsx_bitmap_combine": (_int, [_int, _vp, _vp, _i64, _vp, _vp]),
@@ -120,6 +122,8 @@ _SIGNATURES = {
     "qsx_agg_state_destroy": (_int, [_vp]),
     "qsx_select_cmp_sorted_blocks": (_int, [_int, _i64, C.POINTER(_i64), _pp, _int, _vp, _pp, _pp, _vp, _vp]),
     "qsx_select_cmp_char_blocks": (_int, [_int, _i64, C.POINTER(_i64), _pp, _int, _vp, _int, _pp, _pp, _vp, _vp]),
+    "qsx_select_like_blocks": (_int, [_int, _i64, C.POINTER(_i64), _pp, C.c_char_p, _int, _int, _pp, _pp, _vp, _vp]),
+    "qsx_select_codes_in_set_blocks": (_int, [_int, _i64, C.POINTER(_i64), _pp, _pp, C.POINTER(_i64), _pp, _pp, _vp, _vp]),
     "qsx_select_codes_blocks": (_int, [_int, _i64, C.POINTER(_i64), _pp, C.POINTER(_i32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _pp, _pp,
                                        _vp, _vp]),
     "qsx_select_codes_sorted_blocks": (_int, [_int, _i64, C.POINTER(_i64), _pp, C.POINTER(_i32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _pp, _pp,
@@ -357,6 +361,50 @@ def select_cmp_char(col, op, literal, filter_bitmap=None, stream=None):
     _check(_lib.qsx_select_cmp_char(_ptr(col), width, n, op, C.c_char_p(literal), len(literal), _ptr(filter_bitmap), _ptr(out_bitmap),
                                     _ptr(out_count), _stream(stream)), "qsx_select_cmp_char")
     return out_bitmap, out_count
+
+
+def select_like(col, pattern, negate=False, filter_bitmap=None, stream=None, want_count=True):
+    """K1 with LIKE (negate: NOT LIKE) on a CHAR(width) stripe: col is a uint8 tensor of shape (n, width), pattern a bytes
+    object ('%' any run of bytes, '_' one byte, no escape character).  Returns (bitmap, count); count is None without want_count.
+    Over a dictionary stripe the bitmap is that dictionary's code set for select_codes_in_set."""
+    n, width = col.shape
+    assert col.dtype == torch.uint8 and col.is_contiguous()
+    out_bitmap = new_bitmap(n, col.device)
+    out_count = torch.zeros(1, dtype=torch.int64, device=col.device) if want_count else None
+    _check(_lib.qsx_select_like(_ptr(col), width, n, C.c_char_p(pattern), len(pattern), int(negate), _ptr(filter_bitmap), _ptr(out_bitmap),
+                                _ptr(out_count), _stream(stream)), "qsx_select_like")
+    return out_bitmap, out_count
+
+
+def select_like_blocks(cols, pattern, negate=False, filters=None, stream=None):
+    """select_like on the CHAR(width) stripes of a run of blocks: cols = uint8 tensors of shape (n_b, width)."""
+    width = cols[0].shape[1]
+    nb, outs, counts, _, _, optr, fptr = _run_outputs([c[:, 0] for c in cols], filters)
+    rows = (C.c_int64 * max(nb, 1))(*[c.shape[0] for c in cols])
+    cptr = (C.c_void_p * max(nb, 1))(*[c.data_ptr() if c.numel() else None for c in cols])
+    _check(_lib.qsx_select_like_blocks(width, nb, rows, cptr, C.c_char_p(pattern), len(pattern), int(negate), fptr, optr, _ptr(counts),
+                                       _stream(stream)), "qsx_select_like_blocks")
+    return outs, counts[:nb]
+
+
+def select_codes_in_set(codes, code_set, num_codes, filter_bitmap=None, stream=None, want_count=True):
+    """K1 on a code stripe against a set of codes: code_set is a bitmap of num_codes bits (e.g. select_like over the dictionary);
+    a code >= num_codes is in no set."""
+    n = codes.numel()
+    out_bitmap = new_bitmap(n, codes.device)
+    out_count = torch.zeros(1, dtype=torch.int64, device=codes.device) if want_count else None
+    _check(_lib.qsx_select_codes_in_set(codes.element_size(), _ptr(codes), n, _ptr(code_set), num_codes, _ptr(filter_bitmap),
+                                        _ptr(out_bitmap), _ptr(out_count), _stream(stream)), "qsx_select_codes_in_set")
+    return out_bitmap, out_count
+
+
+def select_codes_in_set_blocks(code_blocks, code_sets, num_codes, filters=None, stream=None):
+    """select_codes_in_set over a run of compressed blocks, one set and one number of codes per block."""
+    nb, outs, counts, rows, cptr, optr, fptr = _run_outputs(code_blocks, filters)
+    _check(_lib.qsx_select_codes_in_set_blocks(code_blocks[0].element_size(), nb, rows, cptr, _ptr_array(code_sets),
+                                               (C.c_int64 * max(nb, 1))(*num_codes), fptr, optr, _ptr(counts), _stream(stream)),
+           "qsx_select_codes_in_set_blocks")
+    return outs, counts[:nb]
 
 
 def select_cmp_sorted(col, op, literal, filter_bitmap=None, stream=None, qtype=None):

@@ -437,6 +437,7 @@ bool HashInnerJoinWorkOrder::executeRun() {
       return t;
     };
     for (const ComparisonPredicate &term : terms) {
+      if (IsLikeComparison(term.comparison)) CheckLikeTerm(term, (term.on_build_side ? build_relation_ : probe_relation_).getAttributeType(term.attribute));
       const Type t = gather_side(term.attribute, term.on_build_side, lhs.ptr);   // (operand types were vetted above)
       if (term.rhs_attribute != kInvalidAttributeID) {
         const Type rt = gather_side(term.rhs_attribute, term.rhs_on_build_side, rhs.ptr);
@@ -445,9 +446,7 @@ bool HashInnerJoinWorkOrder::executeRun() {
                                            first ? nullptr : static_cast<const std::uint64_t *>(cur), static_cast<std::uint64_t *>(nxt), nullptr,
                                            CurrentStream()), "qsx_select_cmp_columns");
       } else if (t.id == kChar) {
-        CheckStatus(qsx_select_cmp_char(lhs.ptr, t.width, m, static_cast<int>(term.comparison), term.literal.text.data(),
-                                        static_cast<int>(term.literal.text.size()), first ? nullptr : static_cast<const std::uint64_t *>(cur),
-                                        static_cast<std::uint64_t *>(nxt), nullptr, CurrentStream()), "qsx_select_cmp_char");
+        SelectCharTerm(term, lhs.ptr, t.width, m, first ? nullptr : static_cast<const std::uint64_t *>(cur), static_cast<std::uint64_t *>(nxt), nullptr);
       } else {
         CheckStatus(qsx_select_cmp(t.id, lhs.ptr, m, static_cast<int>(term.comparison), &term.literal.v,
                                    first ? nullptr : static_cast<const std::uint64_t *>(cur), static_cast<std::uint64_t *>(nxt), nullptr,
@@ -686,6 +685,7 @@ void HashInnerJoinWorkOrder::executeBlock(block_id probe_block_id) {
         return t;
       };
       for (const ComparisonPredicate &term : terms) {
+        if (IsLikeComparison(term.comparison)) CheckLikeTerm(term, (term.on_build_side ? build_relation_ : probe_relation_).getAttributeType(term.attribute));
         const Type t = gather_side(term.attribute, term.on_build_side, lhs.ptr);
         if (term.rhs_attribute != kInvalidAttributeID) {
           if (t.id == kChar || t.id == kVarChar) {
@@ -698,9 +698,7 @@ void HashInnerJoinWorkOrder::executeBlock(block_id probe_block_id) {
                                              static_cast<std::uint64_t *>(nxt), nullptr, CurrentStream()),
                       "qsx_select_cmp_columns");
         } else if (t.id == kChar) {
-          CheckStatus(qsx_select_cmp_char(lhs.ptr, t.width, m, static_cast<int>(term.comparison), term.literal.text.data(),
-                                          static_cast<int>(term.literal.text.size()), first ? nullptr : static_cast<const std::uint64_t *>(cur),
-                                          static_cast<std::uint64_t *>(nxt), nullptr, CurrentStream()), "qsx_select_cmp_char");
+          SelectCharTerm(term, lhs.ptr, t.width, m, first ? nullptr : static_cast<const std::uint64_t *>(cur), static_cast<std::uint64_t *>(nxt), nullptr);
         } else {
           CheckStatus(qsx_select_cmp(t.id, lhs.ptr, m, static_cast<int>(term.comparison), &term.literal.v,
                                      first ? nullptr : static_cast<const std::uint64_t *>(cur),

@@ -6,6 +6,27 @@ namespace quickstep {
 // ---------------------------------------------------------------------------
 // Predicate
 // ---------------------------------------------------------------------------
+void CheckLikeTerm(const ComparisonPredicate &term, const Type &type) {
+  if (type.id != kChar) throw ExecutionError("LIKE / NOT LIKE on an attribute that is not CHAR(n)", QSX_ERR_UNSUPPORTED);
+  if (term.rhs_attribute != kInvalidAttributeID) throw ExecutionError("LIKE / NOT LIKE between two attributes", QSX_ERR_UNSUPPORTED);
+  if (term.literal.text.size() > QSX_MAX_LIKE_PATTERN) throw ExecutionError("LIKE pattern longer than QSX_MAX_LIKE_PATTERN bytes", QSX_ERR_UNSUPPORTED);
+}
+
+void SelectCharTerm(const ComparisonPredicate &term, const void *stripe, int width, std::int64_t n, const std::uint64_t *filter,
+                    std::uint64_t *out_bitmap, std::int64_t *out_count) {
+  if (IsLikeComparison(term.comparison)) {
+    // PatternMatchingUncheckedComparator (PatternMatchingComparators-inl.hpp:190-268)
+    CheckStatus(qsx_select_like(stripe, width, n, term.literal.text.data(), static_cast<int>(term.literal.text.size()),
+                                term.comparison == ComparisonID::kNotLike ? 1 : 0, filter, out_bitmap, out_count, CurrentStream()),
+                "qsx_select_like");
+    return;
+  }
+  // CHAR(n) OP string literal (AsciiStringUncheckedComparator, AsciiStringComparators.hpp:218-251)
+  CheckStatus(qsx_select_cmp_char(stripe, width, n, static_cast<int>(term.comparison), term.literal.text.data(),
+                                  static_cast<int>(term.literal.text.size()), filter, out_bitmap, out_count, CurrentStream()),
+              "qsx_select_cmp_char");
+}
+
 void *Predicate::getMatchesForBlock(const StorageBlock &block, std::int64_t *num_matches, const std::uint64_t *filter) const {
   const std::int64_t n = block.numTuples();
   const std::size_t words = static_cast<std::size_t>((n + 63) / 64);
@@ -15,11 +36,23 @@ void *Predicate::getMatchesForBlock(const StorageBlock &block, std::int64_t *num
   CheckStatus(qsx_device_alloc(8, &count), "qsx_device_alloc(count)");
   bool first = true;
   bool recount = false;
+  std::vector<std::unique_ptr<DeviceBuffer>> code_sets;   // (read by queued kernels: kept until the count has been read)
   for (const ComparisonPredicate &term : conjuncts) {
     const Type &t = block.getRelation().getAttributeType(term.attribute);
     const std::uint64_t *in = first ? filter : static_cast<const std::uint64_t *>(current);
+    const bool like = IsLikeComparison(term.comparison);
+    if (like) CheckLikeTerm(term, t);
     // conjunctions chain the filter through their children (short-circuit)
-    if (const CompressedAttribute *c = block.compressedAttribute(term.attribute)) {
+    if (const CompressedAttribute *c = like ? block.compressedAttribute(term.attribute) : nullptr) {
+      // LIKE on a dictionary-coded attribute: the pattern against the block's dictionary once (its matches are a set of codes),
+      // then code membership over the code stripe — on the sort column too, a set is no range.  The reference runs the matcher
+      // on every decompressed value (PatternMatchingComparators-inl.hpp:190-268); the values are not materialized here.
+      code_sets.emplace_back(new DeviceBuffer(static_cast<std::size_t>((c->num_codes + 63) / 64) * 8 + 8));
+      std::uint64_t *set = static_cast<std::uint64_t *>(code_sets.back()->ptr);
+      SelectCharTerm(term, c->dictionary, c->value_width, c->num_codes, nullptr, set, nullptr);
+      CheckStatus(qsx_select_codes_in_set(c->code_width, c->codes, n, set, c->num_codes, in, static_cast<std::uint64_t *>(next),
+                                          static_cast<std::int64_t *>(count), CurrentStream()), "qsx_select_codes_in_set");
+    } else if (const CompressedAttribute *c = block.compressedAttribute(term.attribute)) {
       // CompressedTupleStorageSubBlock::getMatchesForPredicate (storage/CompressedTupleStorageSubBlock.cpp:160-250):
       // rewrite to a comparison on codes, scan the code stripe
       const PredicateTransformResult r = TransformPredicateOnCompressedAttribute(*c, t.id, term.comparison, term.literal);
@@ -40,10 +73,7 @@ void *Predicate::getMatchesForBlock(const StorageBlock &block, std::int64_t *num
                     "qsx_select_codes");
       }
     } else if (t.id == kChar) {
-      // CHAR(n) OP string literal (AsciiStringUncheckedComparator, AsciiStringComparators.hpp:218-251)
-      CheckStatus(qsx_select_cmp_char(block.stripe(term.attribute), t.width, n, static_cast<int>(term.comparison), term.literal.text.data(),
-                                      static_cast<int>(term.literal.text.size()), in, static_cast<std::uint64_t *>(next),
-                                      static_cast<std::int64_t *>(count), CurrentStream()), "qsx_select_cmp_char");
+      SelectCharTerm(term, block.stripe(term.attribute), t.width, n, in, static_cast<std::uint64_t *>(next), static_cast<std::int64_t *>(count));
     } else if (term.attribute == block.sortColumn()) {
       // the block is sorted on this attribute: SortColumnPredicateEvaluator (storage/ColumnStoreUtil.cpp:40-280)
       CheckStatus(qsx_select_cmp_sorted(t.id, block.stripe(term.attribute), n, static_cast<int>(term.comparison), &term.literal.v, in,
@@ -93,6 +123,7 @@ bool RunPredicateCovers(const Predicate &predicate, const std::vector<BlockRefer
     const StorageBlock &b = *block;
     for (const ComparisonPredicate &term : predicate.conjuncts) {
       const Type &t = b.getRelation().getAttributeType(term.attribute);
+      if (IsLikeComparison(term.comparison)) CheckLikeTerm(term, t);
       if (term.rhs_attribute != kInvalidAttributeID || b.nullBitmap(term.attribute) != nullptr) return false;
       if (b.numTuples() == 0) continue;                 // (an empty block has neither codes nor an order to agree on)
       // a term on the blocks' sort column is a per-block binary search (also on the code stripe of a compressed sort column), a
@@ -141,7 +172,36 @@ void RunPredicateMatches(const Predicate &predicate, const std::vector<BlockRefe
     }
     const std::uint64_t *const *in = first ? in_filters : reinterpret_cast<const std::uint64_t *const *>(cur.data());
     const bool on_sort_column = term.attribute == ref.sortColumn();
-    if (on_sort_column && ref.compressedAttribute(term.attribute) != nullptr) {
+    if (IsLikeComparison(term.comparison) && ref.compressedAttribute(term.attribute) != nullptr) {
+      // LIKE on a dictionary-coded attribute (the sort column included): one launch matches the pattern against the run's
+      // dictionaries — block b's code set —, one tests the code stripes for membership in their block's set
+      std::vector<std::int64_t> dict_rows(nb, 0), num_codes(nb, 0);
+      std::vector<const void *> dictionaries(nb, nullptr);
+      std::vector<std::uint64_t *> sets(nb, nullptr);
+      std::size_t set_words = 0;
+      int value_width = t.width;
+      for (std::size_t b = 0; b < nb; ++b) {
+        const CompressedAttribute *c = blocks[b]->compressedAttribute(term.attribute);
+        stripes[b] = c != nullptr ? c->codes : nullptr;   // (nullptr: an empty block)
+        if (c == nullptr) continue;
+        dict_rows[b] = num_codes[b] = c->num_codes;
+        dictionaries[b] = c->dictionary;
+        value_width = c->value_width;
+        set_words += static_cast<std::size_t>((c->num_codes + 63) / 64) + 1;
+      }
+      out->scratch.emplace_back(new DeviceBuffer(set_words * 8 + 8));
+      std::size_t set_at = 0;
+      for (std::size_t b = 0; b < nb; ++b) {
+        sets[b] = static_cast<std::uint64_t *>(out->scratch.back()->ptr) + set_at;
+        set_at += static_cast<std::size_t>((num_codes[b] + 63) / 64) + (num_codes[b] != 0 ? 1 : 0);
+      }
+      CheckStatus(qsx_select_like_blocks(value_width, static_cast<std::int64_t>(nb), dict_rows.data(), dictionaries.data(), term.literal.text.data(),
+                                         static_cast<int>(term.literal.text.size()), term.comparison == ComparisonID::kNotLike ? 1 : 0, nullptr,
+                                         sets.data(), nullptr, CurrentStream()), "qsx_select_like_blocks");
+      CheckStatus(qsx_select_codes_in_set_blocks(ref.compressedAttribute(term.attribute)->code_width, static_cast<std::int64_t>(nb), rows.data(),
+                                                 stripes.data(), sets.data(), num_codes.data(), in, nxt.data(),
+                                                 static_cast<std::int64_t *>(out->counts->ptr), CurrentStream()), "qsx_select_codes_in_set_blocks");
+    } else if (on_sort_column && ref.compressedAttribute(term.attribute) != nullptr) {
       // the sort column of compressed blocks: the comparison rewritten on every block's own codes
       // (CompressedTupleStorageSubBlock::getMatchesForPredicate), then one search per block on the code stripes
       std::vector<std::int32_t> ops(nb);
@@ -194,6 +254,11 @@ void RunPredicateMatches(const Predicate &predicate, const std::vector<BlockRefe
       CheckStatus(qsx_select_codes_blocks(ref.compressedAttribute(term.attribute)->code_width, static_cast<std::int64_t>(nb), rows.data(),
                                           stripes.data(), ops.data(), firsts.data(), seconds.data(), in, nxt.data(),
                                           static_cast<std::int64_t *>(out->counts->ptr), CurrentStream()), "qsx_select_codes_blocks");
+    } else if (IsLikeComparison(term.comparison)) {
+      // CHAR(n) LIKE pattern on plain stripes (PatternMatchingComparators-inl.hpp:190-268)
+      CheckStatus(qsx_select_like_blocks(t.width, static_cast<std::int64_t>(nb), rows.data(), stripes.data(), term.literal.text.data(),
+                                         static_cast<int>(term.literal.text.size()), term.comparison == ComparisonID::kNotLike ? 1 : 0, in,
+                                         nxt.data(), static_cast<std::int64_t *>(out->counts->ptr), CurrentStream()), "qsx_select_like_blocks");
     } else if (t.id == kChar) {
       // CHAR(n) OP string literal on plain stripes (AsciiStringUncheckedComparator, AsciiStringComparators.hpp:218-251)
       CheckStatus(qsx_select_cmp_char_blocks(t.width, static_cast<std::int64_t>(nb), rows.data(), stripes.data(), static_cast<int>(term.comparison),
@@ -601,6 +666,7 @@ AggregationOperationState::AggregationOperationState(const AggregationStateSpec 
     int in_state = 0;
     for (const ComparisonPredicate &term : spec.predicate->conjuncts) {
       const Type &t = rel.getAttributeType(term.attribute);
+      if (IsLikeComparison(term.comparison)) CheckLikeTerm(term, t);   // (a CHAR(n) term: evaluated by Predicate, below)
       if (t.id == kChar || term.rhs_attribute != kInvalidAttributeID || in_state == QSX_MAX_PRED_TERMS) {
         external_predicate_.conjuncts.push_back(term);   // string comparisons, attribute-vs-attribute, overflow
         continue;

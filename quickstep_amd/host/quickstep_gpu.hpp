@@ -67,8 +67,10 @@ struct DateLit {
   bool operator==(const DateLit &r) const { return year == r.year && month == r.month && day == r.day; }
 };
 static_assert(sizeof(DateLit) == 8, "DateLit occupies 8 bytes");
-// types/operations/comparisons/ComparisonID.hpp:36-42
-enum class ComparisonID { kEqual = 0, kNotEqual, kLess, kLessOrEqual, kGreater, kGreaterOrEqual };
+// types/operations/comparisons/ComparisonID.hpp:36-42.  kLike / kNotLike (PatternMatchingComparison.cpp): a CHAR(n) attribute
+// against a pattern literal, TypedLiteral::Char("PROMO%") — '%' any run of bytes, '_' one byte, no escape character (qsx.h,
+// qsx_select_like).  They are no `op` of the qsx_select_cmp* calls: the first six keep the numbers of qsx_cmp_op_t.
+enum class ComparisonID { kEqual = 0, kNotEqual, kLess, kLessOrEqual, kGreater, kGreaterOrEqual, kLike, kNotLike };
 // expressions/aggregation/AggregationID.hpp
 enum class AggregationID { kCount, kSum, kAvg, kMin, kMax };
 

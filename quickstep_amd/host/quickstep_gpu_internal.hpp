@@ -280,7 +280,16 @@ void CheckRepartition(const char *op, bool has_repartition, const InsertDestinat
 struct RunMatches {
   std::unique_ptr<DeviceBuffer> set_a, set_b, counts;
   std::vector<std::uint64_t *> bitmaps;   // block b's bitmap under the whole conjunction
+  std::vector<std::unique_ptr<DeviceBuffer>> scratch;   // code sets of LIKE terms on coded attributes: read by queued kernels
 };
+// LIKE / NOT LIKE terms (query_context.cpp).  CheckLikeTerm: QSX_ERR_UNSUPPORTED unless the term is CHAR(n) attribute against a
+// pattern literal of at most QSX_MAX_LIKE_PATTERN bytes.  SelectCharTerm: a CHAR(n) attribute against a string literal over a
+// plain stripe of n values — qsx_select_like for the two, qsx_select_cmp_char for the six orderings (whose ComparisonID is
+// the ABI's op).
+inline bool IsLikeComparison(ComparisonID c) { return c == ComparisonID::kLike || c == ComparisonID::kNotLike; }
+void CheckLikeTerm(const ComparisonPredicate &term, const Type &type);
+void SelectCharTerm(const ComparisonPredicate &term, const void *stripe, int width, std::int64_t n, const std::uint64_t *filter,
+                    std::uint64_t *out_bitmap, std::int64_t *out_count);
 bool RunPredicateCovers(const Predicate &predicate, const std::vector<BlockReference> &blocks);
 void RunPredicateMatches(const Predicate &predicate, const std::vector<BlockReference> &blocks, const std::vector<std::int64_t> &rows,
                          const std::uint64_t *const *in_filters, RunMatches *out);

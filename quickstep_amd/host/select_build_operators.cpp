@@ -321,6 +321,7 @@ void SelectWorkOrder::executeOnHost() {
   if (predicate_ != nullptr) {
     for (const ComparisonPredicate &term : predicate_->conjuncts) {
       const Type &t = block->getRelation().getAttributeType(term.attribute);
+      if (IsLikeComparison(term.comparison)) throw ExecutionError("LIKE / NOT LIKE in the host plumbing mode", QSX_ERR_UNSUPPORTED);
       const char *base = static_cast<const char *>(block->stripe(term.attribute));
       for (std::int64_t i = 0; i < n; ++i) {
         if (!match[i]) continue;

@@ -14,6 +14,7 @@ DATE = 6   # the reference's 8-byte DateLit {int32 year; uint8 month, day; 2 byt
 # qsx_cmp_t (types/operations/comparisons/ComparisonID.hpp:36-42)
 EQ, NE, LT, LE, GT, GE = range(6)
 CODE_EQ, CODE_NE, CODE_LT, CODE_GE, CODE_RANGE = range(5)            # qsx_code_cmp_t
+MAX_LIKE_PATTERN = 64                                               # QSX_MAX_LIKE_PATTERN (qsx_select_like)
 # qsx_agg_strategy_t
 AGG_SINGLE_STATE, AGG_COMPACT_KEY, AGG_COLLISION_FREE, AGG_GENERIC = range(4)
 # qsx_agg_fn_t

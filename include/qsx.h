@@ -209,6 +209,61 @@ int qsx_select_like_blocks(int width, int64_t num_blocks, const int64_t *block_r
                            const void *pattern, int pattern_length, int negate, const uint64_t *const *block_filters,
                            uint64_t *const *block_out_bitmaps, int64_t *out_counts_dev, qsx_stream_t stream);
 
+/* A device dictionary of CHAR(width) values: every distinct text gets a dense INT id, so that a CHAR(n) group-by component
+ * of any width can be grouped as an INT column (qsx_agg_*) and turned back into bytes at finalize.  Stands in for the key
+ * side of PackedPayloadHashTable's upsert loop over a CHAR key (storage/PackedPayloadHashTable.hpp:838-909: hash, walk,
+ * compare, insert when absent), which hashes with TypedValue::getHashAsciiString and compares with fastEqualCheck
+ * (types/TypedValue.hpp:575-592, 693-701).  QSX_ABI_VERSION did not change: a caller detects the capability by the presence
+ * of the symbols.
+ *   Text      A value's text is its field up to the first NUL or `width` bytes (1 <= width <= 255); bytes behind the NUL
+ *             never take part.  Two rows get the same id iff their texts are equal.  Comparison is byte-wise (the caveat of
+ *             qsx_select_like: parity with the reference is claimed for bytes < 0x80; nothing folds case).
+ *   Ids       Dense: after any sequence of calls the ids handed out are exactly 0 .. size-1.  Which value gets which id is
+ *             unspecified (like hash order in the reference).  Stable: a value keeps its id across calls and across
+ *             qsx_char_dict_reserve, until qsx_char_dict_clear / _destroy.  A row outside filter_dev (TupleIdSequence bit
+ *             order, MSB first; bits behind row n are ignored) gets id -1 and is not inserted.
+ *   Capacity  max_values (1 .. 2^30) fixes the value store (max_values x width bytes) and the slot table (8 bytes per slot;
+ *             a power of two >= 2 x max_values, at least 16 slots).  A call that meets more new values than fit gives the
+ *             rows it could not place id -1, counts those ROWS in `dropped` and places everything else normally: nothing is
+ *             overwritten, nothing faults, and the call returns QSX_OK, because it is stream-ordered.
+ *   Retry     qsx_char_dict_size waits for the stream and reports `size` and `dropped` (rows dropped since the last
+ *             reserve / clear).  qsx_char_dict_reserve enlarges store and table (never shrinks), keeps every id and zeroes
+ *             `dropped`; repeating the dropped call then gives every row its id.  (reserve waits for its own copy and
+ *             re-hash before it gives the old memory back; it is meant to follow a qsx_char_dict_size.)
+ *   Threads   A dictionary may be interned into from several host threads on several streams (many AggregationWorkOrders
+ *             sharing one state): the library serialises the calls on a dictionary, with a mutex over the enqueue and an
+ *             event so that a call on stream B starts behind the previous call on stream A.  intern / values / clear never
+ *             wait for the device.
+ *   Errors    Without a gfx950 device every entry point but qsx_char_dict_hash returns QSX_ERR_NO_DEVICE in front of any
+ *             argument check.  width outside 1..255, max_values outside 1..2^30, NULL pointers (with n > 0 for the
+ *             stripes): QSX_ERR_INVALID_ARGUMENT.  More than 2^31 - 1028 rows in one call: QSX_ERR_UNSUPPORTED. */
+typedef struct qsx_char_dict qsx_char_dict_t;
+#define QSX_MAX_CHAR_DICT_WIDTH 255
+int qsx_char_dict_create(int width, int64_t max_values, qsx_char_dict_t **out);
+int qsx_char_dict_destroy(qsx_char_dict_t *dict);   /* waits for the device the dictionary lives on */
+/* Forgets every value: size = dropped = 0 (HashTable::clear). */
+int qsx_char_dict_clear(qsx_char_dict_t *dict, qsx_stream_t stream);
+int qsx_char_dict_reserve(qsx_char_dict_t *dict, int64_t max_values, qsx_stream_t stream);
+/* out_ids_dev[i] = the id of col_dev[i] (n fields of `width` bytes), -1 outside the filter: the upsert loop of
+ * PackedPayloadHashTable.hpp:838-909 for one block, with the key compared as TypedValue.hpp:693-701 does. */
+int qsx_char_dict_intern(qsx_char_dict_t *dict, const void *col_dev, int64_t n, const uint64_t *filter_dev,
+                         int32_t *out_ids_dev, qsx_stream_t stream);
+/* The same over a run of blocks (arguments as qsx_select_like_blocks; block_filters or any entry of it may be NULL): the
+ * launches of one call for the whole run, one AggregationWorkOrder per block in the reference. */
+int qsx_char_dict_intern_blocks(qsx_char_dict_t *dict, int64_t num_blocks, const int64_t *block_rows,
+                                const void *const *block_cols, const uint64_t *const *block_filters,
+                                int32_t *const *block_out_ids, qsx_stream_t stream);
+/* Either output may be NULL.  Synchronises the stream. */
+int qsx_char_dict_size(qsx_char_dict_t *dict, int64_t *out_values, int64_t *out_dropped, qsx_stream_t stream);
+/* out_dev[i] = the canonical value of ids_dev[i]: the text zero-filled to `width` (the key bytes a finalize reads back out of
+ * the hash table); `width` zero bytes for -1 and for any id outside [-1, size), which is the caller's error and is never
+ * read out of bounds. */
+int qsx_char_dict_values(qsx_char_dict_t *dict, const int32_t *ids_dev, int64_t n, void *out_dev, qsx_stream_t stream);
+/* The dictionary's 64-bit hash of a text (stands where TypedValue::getHashAsciiString, TypedValue.hpp:575-592, stands: over
+ * the text only): host arithmetic, needs no device.  The slot table takes a value's home slot from the low 32 bits and its
+ * fingerprint from the high 32.  0 for a NULL text or a width outside 1..255. */
+uint64_t qsx_char_dict_hash(const void *text, int width);
+
 /* qsx_select_cmp on the SORT COLUMN of a sorted column store (ascending, no NULLs in the first n rows): the matches are
  * one row range found by two searches, not a scan.  Replaces SortColumnPredicateEvaluator::
  * EvaluatePredicateForUncompressedSortColumn (storage/ColumnStoreUtil.cpp:40-280) as called from

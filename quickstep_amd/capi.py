@@ -66,6 +66,15 @@ _SIGNATURES = {
     "qsx_select_cmp_char": (_int, [_vp, _int, _i64, _int, C.c_char_p, _int, _vp, _vp, _vp, _vp]),
     "qsx_select_cmp_columns": (_int, [_int, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp]),
     "qsx_select_like": (_int, [_vp, _int, _i64, C.c_char_p, _int, _int, _vp, _vp, _vp, _vp]),
+    "qsx_char_dict_create": (_int, [_int, _i64, _pp]),
+    "qsx_char_dict_destroy": (_int, [_vp]),
+    "qsx_char_dict_clear": (_int, [_vp, _vp]),
+    "qsx_char_dict_reserve": (_int, [_vp, _i64, _vp]),
+    "qsx_char_dict_intern": (_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "qsx_char_dict_intern_blocks": (_int, [_vp, _i64, C.POINTER(_i64), _pp, _pp, _pp, _vp]),
+    "qsx_char_dict_size": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), _vp]),
+    "qsx_char_dict_values": (_int, [_vp, _vp, _i64, _vp, _vp]),
+    "qsx_char_dict_hash": (C.c_uint64, [C.c_char_p, _int]),
     "qsx_select_codes": (_int, [_int, _vp, _i64, _int, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
     "qsx_select_codes_in_set": (_int, [_int, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "qsx_select_codes_sorted": (_int, [_int, _vp, _i64, _int, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
@@ -385,6 +394,76 @@ def select_like_blocks(cols, pattern, negate=False, filters=None, stream=None):
     _check(_lib.qsx_select_like_blocks(width, nb, rows, cptr, C.c_char_p(pattern), len(pattern), int(negate), fptr, optr, _ptr(counts),
                                        _stream(stream)), "qsx_select_like_blocks")
     return outs, counts[:nb]
+
+
+def char_dict_hash(text, width):
+    """The dictionary's 64-bit hash of a CHAR(width) field given as bytes (qsx_char_dict_hash): host arithmetic, needs no GPU.
+    The field is padded with NULs to `width`; only its text (up to the first NUL) takes part."""
+    field = bytes(text)[:width].ljust(width, b"\0")
+    return _lib.qsx_char_dict_hash(C.c_char_p(field), width)
+
+
+class CharDict:
+    """A device dictionary of CHAR(width) values (qsx_char_dict_*): interns uint8 tensors of shape (n, width) into dense int32
+    ids, so that a CHAR(n) group-by component of any width can be grouped as an INT column."""
+
+    def __init__(self, width, max_values):
+        self.width = width
+        h = C.c_void_p()
+        _check(_lib.qsx_char_dict_create(width, max_values, C.byref(h)), "qsx_char_dict_create")
+        self._h = h
+
+    def intern(self, col, filter_bitmap=None, stream=None, out=None):
+        """ids int32[n]: equal texts get equal ids, rows outside the filter (and rows dropped for lack of room) get -1."""
+        n, width = col.shape
+        assert col.dtype == torch.uint8 and col.is_contiguous() and width == self.width
+        ids = out if out is not None else torch.empty(n, dtype=torch.int32, device=col.device)
+        _check(_lib.qsx_char_dict_intern(self._h, _ptr(col), n, _ptr(filter_bitmap), _ptr(ids), _stream(stream)), "qsx_char_dict_intern")
+        return ids
+
+    def intern_blocks(self, cols, filters=None, stream=None):
+        """intern over a run of blocks: cols = uint8 tensors of shape (n_b, width); returns one id tensor per block."""
+        nb = len(cols)
+        assert all(c.dtype == torch.uint8 and c.is_contiguous() and c.shape[1] == self.width for c in cols)
+        outs = [torch.empty(c.shape[0], dtype=torch.int32, device=c.device) for c in cols]
+        rows = (C.c_int64 * max(nb, 1))(*[c.shape[0] for c in cols])
+        cptr = (C.c_void_p * max(nb, 1))(*[c.data_ptr() if c.numel() else None for c in cols])
+        optr = (C.c_void_p * max(nb, 1))(*[o.data_ptr() if o.numel() else None for o in outs])
+        fptr = None
+        if filters is not None:
+            fptr = (C.c_void_p * max(nb, 1))(*[f.data_ptr() if f is not None and f.numel() else None for f in filters])
+        _check(_lib.qsx_char_dict_intern_blocks(self._h, nb, rows, cptr, fptr, optr, _stream(stream)), "qsx_char_dict_intern_blocks")
+        return outs
+
+    def size(self, stream=None):
+        """(values in the dictionary, rows dropped since the last reserve / clear).  Waits for the stream."""
+        values, dropped = C.c_int64(), C.c_int64()
+        _check(_lib.qsx_char_dict_size(self._h, C.byref(values), C.byref(dropped), _stream(stream)), "qsx_char_dict_size")
+        return values.value, dropped.value
+
+    def reserve(self, max_values, stream=None):
+        _check(_lib.qsx_char_dict_reserve(self._h, max_values, _stream(stream)), "qsx_char_dict_reserve")
+
+    def values(self, ids, stream=None):
+        """uint8 (n, width): the canonical (zero-filled) value of every id, zero bytes for -1."""
+        assert ids.dtype == torch.int32 and ids.is_contiguous()
+        out = torch.empty((ids.numel(), self.width), dtype=torch.uint8, device=ids.device)
+        _check(_lib.qsx_char_dict_values(self._h, _ptr(ids), ids.numel(), _ptr(out), _stream(stream)), "qsx_char_dict_values")
+        return out
+
+    def clear(self, stream=None):
+        _check(_lib.qsx_char_dict_clear(self._h, _stream(stream)), "qsx_char_dict_clear")
+
+    def close(self):
+        if self._h is not None:
+            _check(_lib.qsx_char_dict_destroy(self._h), "qsx_char_dict_destroy")
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def select_codes_in_set(codes, code_set, num_codes, filter_bitmap=None, stream=None, want_count=True):

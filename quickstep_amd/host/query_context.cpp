@@ -598,6 +598,22 @@ AggregationOperationState::AggregationOperationState(const AggregationStateSpec 
   config_.strategy = spec.group_by.empty() ? QSX_AGG_SINGLE_STATE : spec.strategy;
   config_.num_keys = static_cast<int>(spec.group_by.size());
   for (std::size_t k = 0; k < spec.group_by.size(); ++k) config_.key_column[k] = column_of(spec.group_by[k]);
+  // GROUP BY CHAR(n): the widths the state packs itself (1, 2, 4, 8 bytes under COMPACT_KEY) keep their path; every other
+  // CHAR group-by attribute is presented as an INT column of ids out of a device dictionary of its values
+  for (std::size_t k = 0; k < spec.group_by.size(); ++k) {
+    const Type &t = rel.getAttributeType(spec.group_by[k]);
+    const bool packs = t.width == 1 || t.width == 2 || t.width == 4 || t.width == 8;
+    if (t.id != kChar || (packs && config_.strategy != QSX_AGG_GENERIC) || internedKeyOf(config_.key_column[k]) >= 0) continue;
+    InternedKey key;
+    key.column = config_.key_column[k];
+    key.attribute = spec.group_by[k];
+    key.width = t.width;
+    key.capacity = spec.estimated_num_groups > 16 ? spec.estimated_num_groups : 16;
+    if (key.capacity > (std::int64_t(1) << 30)) key.capacity = std::int64_t(1) << 30;
+    interned_.push_back(key);
+    config_.column_type[key.column] = kInt;
+    config_.column_width[key.column] = 4;
+  }
   int num_main = 0;
   ExpressionFlattener flattener(column_of, spec.integer_argument_arithmetic ? &rel : nullptr);
   for (std::size_t a = 0; a < spec_.aggregates.size(); ++a) {
@@ -606,6 +622,9 @@ AggregationOperationState::AggregationOperationState(const AggregationStateSpec 
       spec_.aggregates[a].argument_expression = nullptr;
     }
     const AggregateSpec &ag = spec_.aggregates[a];
+    if (ag.is_distinct && !interned_.empty()) {   // (finalizeWithDistinct lines its result sets up by sorting on key VALUES)
+      throw ExecutionError("DISTINCT aggregate beside a CHAR(n) group-by key that is interned into ids", QSX_ERR_UNSUPPORTED);
+    }
     if (ag.argument_expression != nullptr && ag.is_distinct) {
       // DISTINCT over an arithmetic expression (Distinct.test:58-72 COUNT(DISTINCT x % y) is such a query): the distinctify
       // key is (group-by..., value of the expression); the value column is computed per block (qsx_eval_expression)
@@ -683,11 +702,107 @@ AggregationOperationState::AggregationOperationState(const AggregationStateSpec 
   config_.num_entries = spec.collision_free_num_entries;
   // all_distinct_ (:126-127, 620-628): no upsert into the final table per block, it is filled from the distinctify tables
   if (num_main > 0 || distinctify_.empty()) CheckStatus(qsx_agg_state_create(&config_, &state_), "qsx_agg_state_create");
+  try {
+    for (InternedKey &key : interned_) CheckStatus(qsx_char_dict_create(key.width, key.capacity, &key.dictionary), "qsx_char_dict_create");
+  } catch (...) {
+    for (InternedKey &key : interned_) if (key.dictionary != nullptr) qsx_char_dict_destroy(key.dictionary);
+    if (state_ != nullptr) qsx_agg_state_destroy(state_);
+    throw;
+  }
 }
 
 AggregationOperationState::~AggregationOperationState() {
   if (state_ != nullptr) qsx_agg_state_destroy(state_);
   if (coded_state_ != nullptr) qsx_agg_state_destroy(coded_state_);
+  for (InternedKey &key : interned_) if (key.dictionary != nullptr) qsx_char_dict_destroy(key.dictionary);
+}
+
+int AggregationOperationState::internedKeyOf(std::size_t column) const {
+  for (std::size_t i = 0; i < interned_.size(); ++i) {
+    if (static_cast<std::size_t>(interned_[i].column) == column) return static_cast<int>(i);
+  }
+  return -1;
+}
+
+struct AggregationOperationState::InternScratch {
+  std::vector<std::unique_ptr<DeviceBuffer>> buffers;
+  void *take(std::size_t bytes) {
+    buffers.emplace_back(new DeviceBuffer(bytes + 16));
+    return buffers.back()->ptr;
+  }
+};
+
+// The id stripes of the interned keys for the rows of `requests` (a block, or the blocks of a run), ready when this returns.
+//   a plain stripe             qsx_char_dict_intern / _intern_blocks under the request's filter, NULL rows kept out of it
+//                              (PackedPayloadHashTable.hpp:861-867 skips a tuple with a NULL key; their id is -1 and the
+//                              attribute's null bitmap, which travels with the id column, keeps them out of the state)
+//   a dictionary-coded stripe  the block's DICTIONARY is interned (num_codes values) and the code stripe mapped through the
+//                              resulting id array (qsx_decode_codes): the values are never decoded, as with LIKE on codes
+// An intern is stream-ordered and cannot fail for lack of room: it drops rows instead.  So the dictionary's counters are read
+// behind it (one synchronisation); on a drop the dictionary is enlarged at least fourfold and the interns are repeated — ids
+// that were handed out stay — before any of them reaches the state.  One block or run at a time per state: `dropped` belongs
+// to the dictionary, not to a call.
+void AggregationOperationState::internBlocks(std::vector<InternRequest> *requests, InternScratch *scratch) {
+  if (interned_.empty() || requests->empty()) return;
+  std::vector<std::unique_ptr<DeviceBuffer>> not_null;   // the intern filters of nullable keys
+  for (InternRequest &r : *requests) r.ids.assign(interned_.size(), nullptr);
+  std::lock_guard<std::mutex> lock(intern_mutex_);
+  for (std::size_t k = 0; k < interned_.size(); ++k) {
+    InternedKey &key = interned_[k];
+    std::vector<std::int64_t> rows;
+    std::vector<const void *> cols;
+    std::vector<const std::uint64_t *> filters;
+    std::vector<std::int32_t *> outs;
+    struct Coded { const CompressedAttribute *attribute; std::int64_t n; std::int32_t *code_ids, *out; };
+    std::vector<Coded> coded;
+    for (InternRequest &r : *requests) {
+      const std::int64_t n = r.block->numTuples();
+      std::int32_t *ids = static_cast<std::int32_t *>(scratch->take(static_cast<std::size_t>(n) * 4));
+      r.ids[k] = ids;
+      if (n == 0) continue;
+      const CompressedAttribute *ca = r.block->compressedAttribute(key.attribute);
+      if (ca != nullptr && ca->kind == CompressedAttribute::kDictionary && !r.block->valuesMaterialized(key.attribute)) {
+        // (one more entry than codes: the dictionary's NULL code, num_codes, maps to -1)
+        coded.push_back(Coded{ca, n, static_cast<std::int32_t *>(scratch->take((static_cast<std::size_t>(ca->num_codes) + 1) * 4)), ids});
+        continue;
+      }
+      const std::uint64_t *filter = r.filter;
+      if (r.block->nullBitmap(key.attribute) != nullptr) {
+        std::unique_ptr<DeviceBuffer> keep = NotNullFilter(*r.block, {key.attribute}, r.filter);
+        if (keep != nullptr) {
+          filter = static_cast<const std::uint64_t *>(keep->ptr);
+          not_null.push_back(std::move(keep));
+        }
+      }
+      rows.push_back(n);
+      cols.push_back(r.block->stripe(key.attribute));
+      filters.push_back(filter);
+      outs.push_back(ids);
+    }
+    for (;;) {
+      if (rows.size() == 1) {
+        CheckStatus(qsx_char_dict_intern(key.dictionary, cols[0], rows[0], filters[0], outs[0], CurrentStream()), "qsx_char_dict_intern");
+      } else if (!rows.empty()) {
+        CheckStatus(qsx_char_dict_intern_blocks(key.dictionary, static_cast<std::int64_t>(rows.size()), rows.data(), cols.data(), filters.data(),
+                                                outs.data(), CurrentStream()), "qsx_char_dict_intern_blocks");
+      }
+      for (const Coded &c : coded) {
+        CheckStatus(qsx_char_dict_intern(key.dictionary, c.attribute->dictionary, c.attribute->num_codes, nullptr, c.code_ids, CurrentStream()),
+                    "qsx_char_dict_intern(dictionary)");
+        CheckStatus(qsx_memset_device(c.code_ids + c.attribute->num_codes, 0xFF, 4, CurrentStream()), "qsx_memset_device");
+      }
+      std::int64_t values = 0, dropped = 0;
+      CheckStatus(qsx_char_dict_size(key.dictionary, &values, &dropped, CurrentStream()), "qsx_char_dict_size");
+      if (dropped == 0) break;
+      if (key.capacity >= (std::int64_t(1) << 30)) throw ExecutionError("GROUP BY CHAR(n): more than 2^30 distinct values", QSX_ERR_TOO_MANY_GROUPS);
+      key.capacity = key.capacity * 4 < (std::int64_t(1) << 30) ? key.capacity * 4 : (std::int64_t(1) << 30);
+      CheckStatus(qsx_char_dict_reserve(key.dictionary, key.capacity, CurrentStream()), "qsx_char_dict_reserve");
+    }
+    for (const Coded &c : coded) {
+      CheckStatus(qsx_decode_codes(c.attribute->code_width, c.attribute->codes, c.n, c.code_ids, 4, c.out, CurrentStream()), "qsx_decode_codes(ids)");
+    }
+  }
+  CheckStatus(qsx_stream_synchronize(CurrentStream()), "qsx_stream_synchronize");   // (the filters in not_null go back to the pool)
 }
 
 void AggregationOperationState::initialize(std::size_t state_partition_id) {
@@ -791,11 +906,19 @@ void AggregationOperationState::aggregateBlock(const StorageBlock &block, const 
   for (std::size_t i = 0; i < column_attr_.size() && !any_nulls; ++i) {
     const CompressedAttribute *ca = block.compressedAttribute(column_attr_[i]);
     const int type = config_.column_type[i];
-    if (ca != nullptr && type != kChar && !block.valuesMaterialized(column_attr_[i])) {
+    if (ca != nullptr && type != kChar && internedKeyOf(i) < 0 && !block.valuesMaterialized(column_attr_[i])) {
       code_width[i] = ca->code_width;
       any_coded = true;
     }
   }
+  // the id stripes of the interned CHAR(n) keys stand where the attribute's stripe would (under the filter the update gets)
+  InternScratch intern_scratch;
+  std::vector<InternRequest> intern(1, InternRequest{&block, lip_filter, {}});
+  if (n > 0) internBlocks(&intern, &intern_scratch);
+  const auto stripe_of = [&](std::size_t i) -> const void * {
+    const int key = internedKeyOf(i);
+    return key >= 0 && n > 0 ? intern[0].ids[key] : block.stripe(column_attr_[i]);
+  };
   if (any_coded && n > 0) {
     bool use_coded = false;
     {
@@ -817,7 +940,7 @@ void AggregationOperationState::aggregateBlock(const StorageBlock &block, const 
       std::int32_t dict_entries[QSX_MAX_COLUMNS] = {};
       for (std::size_t i = 0; i < column_attr_.size(); ++i) {
         const CompressedAttribute *ca = code_width[i] != 0 ? block.compressedAttribute(column_attr_[i]) : nullptr;
-        cols[i] = ca != nullptr ? ca->codes : block.stripe(column_attr_[i]);
+        cols[i] = ca != nullptr ? ca->codes : stripe_of(i);
         dicts[i] = ca != nullptr && ca->kind == CompressedAttribute::kDictionary ? ca->dictionary : nullptr;
         dict_entries[i] = dicts[i] != nullptr ? static_cast<std::int32_t>(ca->num_codes) : 0;
       }
@@ -836,7 +959,7 @@ void AggregationOperationState::aggregateBlock(const StorageBlock &block, const 
     }
   }
   const void *cols[QSX_MAX_COLUMNS];
-  for (std::size_t i = 0; i < column_attr_.size(); ++i) cols[i] = block.stripe(column_attr_[i]);
+  for (std::size_t i = 0; i < column_attr_.size(); ++i) cols[i] = stripe_of(i);
   if (any_nulls) {
     CheckStatus(qsx_agg_update_nullable(state_, cols, nulls, n, lip_filter, CurrentStream()), "qsx_agg_update_nullable");
   } else {
@@ -870,6 +993,18 @@ void AggregationOperationState::aggregateBlocks(const std::vector<BlockReference
   std::vector<BlockReference> coded_refs;
   bool any_coded_filter = false;
   const bool state_allows = state_ != nullptr && distinctify_.empty() && external_predicate_.conjuncts.empty();
+  // interned CHAR(n) keys: their id stripes are made for the whole run at once (internBlocks) and then stand where the
+  // attribute's stripe would; until then the column's entry is a placeholder
+  InternScratch intern_scratch;
+  std::vector<InternRequest> intern;
+  struct Placeholder { bool coded; std::size_t at; std::size_t request; int key; };
+  std::vector<Placeholder> placeholders;
+  const auto stripe_or_placeholder = [&](const StorageBlock &block, std::size_t c, bool coded, std::size_t at) -> const void * {
+    const int key = internedKeyOf(c);
+    if (key < 0) return block.stripe(column_attr_[c]);
+    placeholders.push_back(Placeholder{coded, at, intern.size() - 1, key});
+    return nullptr;
+  };
   for (std::size_t i = 0; i < blocks.size(); ++i) {
     const StorageBlock &block = *blocks[i];
     const std::uint64_t *filter = i < lip_filters.size() ? lip_filters[i] : nullptr;
@@ -880,7 +1015,7 @@ void AggregationOperationState::aggregateBlocks(const std::vector<BlockReference
       // null bitmaps travel with single-block calls (qsx_agg_update_nullable)
       if (block.nullBitmap(column_attr_[c]) != nullptr) in_run = false;
       const CompressedAttribute *ca = block.compressedAttribute(column_attr_[c]);
-      if (ca != nullptr && config_.column_type[c] != kChar && !block.valuesMaterialized(column_attr_[c])) {
+      if (ca != nullptr && config_.column_type[c] != kChar && internedKeyOf(c) < 0 && !block.valuesMaterialized(column_attr_[c])) {
         code_width[c] = ca->code_width;          // aggregated on its codes, like aggregateBlock does
         any_coded = true;
       }
@@ -906,16 +1041,18 @@ void AggregationOperationState::aggregateBlocks(const std::vector<BlockReference
         // a block that compressed an operand differently than the block the coded state was created for (another code width, or
         // not at all): its values — stripe() decodes them once — join the run of plain stripes instead of a call of their own
         rows.push_back(block.numTuples());
-        for (std::size_t c = 0; c < column_attr_.size(); ++c) cols.push_back(block.stripe(column_attr_[c]));
+        if (!interned_.empty()) intern.push_back(InternRequest{&block, filter, {}});
+        for (std::size_t c = 0; c < column_attr_.size(); ++c) cols.push_back(stripe_or_placeholder(block, c, false, cols.size()));
         filters.push_back(filter);
         any_filter = any_filter || filter != nullptr;
         continue;
       }
+      if (!interned_.empty()) intern.push_back(InternRequest{&block, filter, {}});
       coded_rows.push_back(block.numTuples());
       coded_refs.push_back(blocks[i]);
       for (std::size_t c = 0; c < column_attr_.size(); ++c) {
         const CompressedAttribute *ca = code_width[c] != 0 ? block.compressedAttribute(column_attr_[c]) : nullptr;
-        coded_cols.push_back(ca != nullptr ? ca->codes : block.stripe(column_attr_[c]));
+        coded_cols.push_back(ca != nullptr ? ca->codes : stripe_or_placeholder(block, c, true, coded_cols.size()));
         coded_dicts.push_back(ca != nullptr && ca->kind == CompressedAttribute::kDictionary ? ca->dictionary : nullptr);
         coded_entries.push_back(coded_dicts.back() != nullptr ? static_cast<std::int32_t>(ca->num_codes) : 0);
       }
@@ -928,10 +1065,13 @@ void AggregationOperationState::aggregateBlocks(const std::vector<BlockReference
       continue;
     }
     rows.push_back(block.numTuples());
-    for (std::size_t c = 0; c < column_attr_.size(); ++c) cols.push_back(block.stripe(column_attr_[c]));
+    if (!interned_.empty()) intern.push_back(InternRequest{&block, filter, {}});
+    for (std::size_t c = 0; c < column_attr_.size(); ++c) cols.push_back(stripe_or_placeholder(block, c, false, cols.size()));
     filters.push_back(filter);
     any_filter = any_filter || filter != nullptr;
   }
+  internBlocks(&intern, &intern_scratch);
+  for (const Placeholder &p : placeholders) (p.coded ? coded_cols : cols)[p.at] = intern[p.request].ids[p.key];
   RunMatches coded_matches;
   if (!coded_rows.empty() && coded_predicate_external_) {
     // the predicate over the run's code stripes: every term one launch, rewritten on every block's own codes
@@ -1159,7 +1299,14 @@ void AggregationOperationState::finalizeAggregate(std::size_t partition, std::si
   void *val_cols[QSX_MAX_AGGS];
   std::uint8_t *null_cols[QSX_MAX_AGGS] = {};
   std::vector<std::unique_ptr<DeviceBuffer>> null_flags;
-  for (int k = 0; k < config_.num_keys; ++k) key_cols[k] = out->stripe(k);
+  // an interned CHAR(n) key is finalized as the ids the state grouped by, into scratch; its bytes follow below
+  std::vector<std::unique_ptr<DeviceBuffer>> key_ids(static_cast<std::size_t>(config_.num_keys));
+  for (int k = 0; k < config_.num_keys; ++k) {
+    key_cols[k] = out->stripe(k);
+    if (internedKeyOf(static_cast<std::size_t>(config_.key_column[k])) < 0) continue;
+    key_ids[k].reset(new DeviceBuffer(static_cast<std::size_t>(out->capacity()) * 4 + 16));
+    key_cols[k] = key_ids[k]->ptr;
+  }
   for (int a = 0; a < config_.num_aggs; ++a) {
     val_cols[a] = out->stripe(config_.num_keys + a);
     // result types of SUM / AVG / MIN / MAX are nullable (AggregationHandleSum::getResultType ...->getNullableVersion()):
@@ -1178,6 +1325,12 @@ void AggregationOperationState::finalizeAggregate(std::size_t partition, std::si
   // a key wider than 8 bytes is grouped by its 64-bit hash and verified: two keys under one hash void the result
   if (written == QSX_GROUPS_HASH_COLLISION) throw ExecutionError("qsx_agg_finalize: wide group-by key", QSX_ERR_HASH_COLLISION);
   if (written > out->capacity()) throw ExecutionError("qsx_agg_finalize: more groups than the output block holds", QSX_ERR_CAPACITY);
+  for (int k = 0; k < config_.num_keys && written > 0; ++k) {
+    if (key_ids[k] == nullptr) continue;
+    const InternedKey &key = interned_[static_cast<std::size_t>(internedKeyOf(static_cast<std::size_t>(config_.key_column[k])))];
+    CheckStatus(qsx_char_dict_values(key.dictionary, static_cast<const std::int32_t *>(key_ids[k]->ptr), written, out->stripe(k), CurrentStream()),
+                "qsx_char_dict_values");
+  }
   for (int a = 0; a < config_.num_aggs && written > 0; ++a) {
     if (null_cols[a] == nullptr) continue;
     // byte flags -> TupleIdSequence-ordered bitmap: a scan of 1-byte "codes" for flag >= 1

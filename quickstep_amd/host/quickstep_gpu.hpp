@@ -555,6 +555,27 @@ class AggregationOperationState {
   struct Distinctify;
   std::vector<std::unique_ptr<Distinctify>> distinctify_;
   void finalizeWithDistinct(InsertDestination *dest);
+  // GROUP BY CHAR(n): a CHAR group-by attribute whose width is not 1, 2, 4 or 8, and every CHAR group-by attribute of the
+  // GENERIC strategy, reaches the state as an INT column of ids out of a device dictionary of its values (qsx_char_dict_*:
+  // equal texts, equal ids); finalize turns the ids back into bytes.  The ids are local to this state: it is neither
+  // exchanged across ranks nor combined with DISTINCT aggregates (which sort on key values).
+  struct InternedKey {
+    int column = 0;                      // column of config_
+    attribute_id attribute = 0;
+    int width = 0;
+    qsx_char_dict_t *dictionary = nullptr;
+    std::int64_t capacity = 0;
+  };
+  std::vector<InternedKey> interned_;
+  std::mutex intern_mutex_;              // intern, look for dropped rows, reserve, repeat: one block (or run) at a time
+  int internedKeyOf(std::size_t column) const;   // index into interned_, or -1
+  struct InternRequest {                 // one block's rows that need the ids of the interned keys
+    const StorageBlock *block;
+    const std::uint64_t *filter;
+    std::vector<void *> ids;             // out: one id stripe per interned key (they live in the InternScratch)
+  };
+  struct InternScratch;                  // the device buffers behind the id stripes of one call
+  void internBlocks(std::vector<InternRequest> *requests, InternScratch *scratch);
 };
 
 // ---------------------------------------------------------------------------

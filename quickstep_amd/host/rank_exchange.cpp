@@ -41,6 +41,12 @@ void RankGroup::synchronize() { CheckStatus(qsx_comm_synchronize(comm_, CurrentS
 void RankGroup::abort() noexcept { (void)qsx_comm_abort(comm_); }
 
 void AggregationOperationState::mergeAcrossRanks(qsx_comm_t *comm) {
+  // Ids of an interned CHAR(n) group-by key are local to this rank's dictionary: two ranks give the same text different
+  // ids.  Every rank holds the same spec and so takes this exit alike, in front of the first collective.
+  if (!interned_.empty()) {
+    throw ExecutionError("AggregationOperationState::mergeAcrossRanks: a CHAR(n) group-by key interned into rank-local ids is not exchanged",
+                         QSX_ERR_UNSUPPORTED);
+  }
   // The local part first, and its outcome agreed on with the peers (qsx_comm_agree): a rank that fails here must not leave
   // the others inside the merge's collectives.  (The collectives agree on their own scratch the same way, csrc/aggregate.hip.)
   int status = QSX_OK;

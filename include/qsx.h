@@ -1006,7 +1006,12 @@ int qsx_agg_num_groups(qsx_agg_state_t *state, int64_t *out_groups, qsx_stream_t
  *   out_groups_dev int64 on device: rows written — or QSX_GROUPS_HASH_COLLISION: the state groups by a key wider
  *                 than 8 bytes and two different keys shared their 64-bit hash (every group carries MIN and MAX of its
  *                 packed key words, MIN != MAX somewhere proves it).  Nothing of the output may be used then; the
- *                 caller reports QSX_ERR_HASH_COLLISION / re-runs the operator.  Expected once in ~2^64 / groups^2 states. */
+ *                 caller reports QSX_ERR_HASH_COLLISION / re-runs the operator.  Expected once in ~2^64 / groups^2 states.
+ * Every output row is defined by a successful call, whatever the buffers held before: rows [0, min(groups, capacity)) hold
+ * the groups, rows [min(groups, capacity), capacity) of every key, value and null column are zero, and *out_groups_dev is
+ * written (not added to) — the caller pre-zeroes nothing.  The call waits for `stream`: when it returns QSX_OK the
+ * outputs are complete (a table that had to grow, or whose spill log had to drain, was finalized a second time over the
+ * grown table before the call returned).  After an error return the outputs are undefined. */
 #define QSX_GROUPS_HASH_COLLISION (-1ll)
 int qsx_agg_finalize(qsx_agg_state_t *state, int partition, int num_partitions,
                      void *const *out_key_cols, void *const *out_val_cols,

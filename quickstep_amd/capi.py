@@ -1230,7 +1230,8 @@ class AggState:
         return v.value
 
     def finalize(self, device, partition=0, num_partitions=1, capacity=None, stream=None):
-        """K10: returns (key columns, value columns, null columns (uint8), groups int64[1])."""
+        """K10: returns (key columns, value columns, null columns (uint8), groups int64[1]).  qsx_agg_finalize defines every
+        output row — zero behind the groups — and the group count, so nothing is filled here."""
         cfg = self.config
         if capacity is None:
             capacity = max(self.num_groups(stream), 1)
@@ -1238,13 +1239,13 @@ class AggState:
         for k in range(cfg.num_keys):
             w = cfg.column_width[cfg.key_column[k]]
             dt = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[w]
-            keys.append(torch.zeros(capacity, dtype=dt, device=device))
+            keys.append(torch.empty(capacity, dtype=dt, device=device))
         vals, nulls = [], []
         for a in range(cfg.num_aggs):
             dt = getattr(torch, T.agg_output_dtype(cfg, a))
-            vals.append(torch.zeros(capacity, dtype=dt, device=device))
-            nulls.append(torch.zeros(capacity, dtype=torch.uint8, device=device))
-        groups = torch.zeros(1, dtype=torch.int64, device=device)
+            vals.append(torch.empty(capacity, dtype=dt, device=device))
+            nulls.append(torch.empty(capacity, dtype=torch.uint8, device=device))
+        groups = torch.empty(1, dtype=torch.int64, device=device)
         _check(_lib.qsx_agg_finalize(self._h, partition, num_partitions, _ptr_array(keys), _ptr_array(vals),
                                      _ptr_array(nulls), capacity, _ptr(groups), _stream(stream)), "qsx_agg_finalize")
         return keys, vals, nulls, groups

@@ -152,6 +152,53 @@ __global__ void publish_control_kernel(const unsigned long long *__restrict__ co
   __hip_atomic_store(&host_slot[3], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// qsx_agg_state_clear of a small hash-strategy state in ONE launch (the memsets it replaces cost a launch each, and a
+// table of a few thousand slots is reset in less time than one launch takes): key words to the empty marker, every state
+// column to its identity, the directory entries and counters, the spill-log records a previous run touched, the control
+// words.  Workgroup 0 alone resets the log and the control words, in that order behind a barrier: the number of records to
+// reset is read from the control words this kernel zeroes.
+struct ClearDesc {
+  unsigned long long *image;         // [slots key words][num_cols columns of slots words]
+  unsigned long long slots;          // cap + 1
+  int num_cols;
+  ColKinds kinds;
+  unsigned long long *dir_entries;   // nullptr: no directory
+  unsigned long long dir_words;
+  unsigned int *dir_ngids;           // 4 counter words
+  unsigned long long *log;           // nullptr: not growable
+  int log_stride;
+  unsigned int log_cap;
+  unsigned long long *control;       // 8 words
+};
+__global__ __launch_bounds__(kABlock) void clear_hash_state_kernel(ClearDesc c) {
+  const unsigned long long image_words = c.slots * static_cast<unsigned long long>(c.num_cols + 1);
+  const unsigned long long total = image_words + (c.dir_entries != nullptr ? c.dir_words : 0ull);
+  for (unsigned long long i = static_cast<unsigned long long>(blockIdx.x) * kABlock + threadIdx.x; i < total;
+       i += static_cast<unsigned long long>(gridDim.x) * kABlock) {
+    if (i < c.slots) {
+      c.image[i] = kEmptyCode;
+    } else if (i < image_words) {
+      c.image[i] = static_cast<unsigned long long>(acc_identity(c.kinds.kind[static_cast<int>(i / c.slots) - 1]));
+    } else {
+      c.dir_entries[i - image_words] = ~0ull;
+    }
+  }
+  if (blockIdx.x != 0) return;
+  if (c.dir_entries != nullptr && threadIdx.x < 4) c.dir_ngids[threadIdx.x] = 0u;
+  unsigned long long records = 0;
+  if (c.log != nullptr) {
+    const unsigned int left = *reinterpret_cast<const unsigned int *>(c.control + 3);
+    records = left < c.log_cap ? left : c.log_cap;
+  }
+  __syncthreads();
+  const unsigned long long log_words = records * static_cast<unsigned long long>(c.log_stride);
+  for (unsigned long long i = threadIdx.x; i < log_words; i += kABlock) {
+    const int w = static_cast<int>(i % c.log_stride);
+    c.log[i] = w == 0 ? kEmptyCode : static_cast<unsigned long long>(acc_identity(c.kinds.kind[w - 1]));
+  }
+  if (threadIdx.x < 8) c.control[threadIdx.x] = 0ull;
+}
+
 // ---------------------------------------------------------------------------
 // finalize
 // ---------------------------------------------------------------------------
@@ -269,35 +316,82 @@ __device__ __forceinline__ unsigned long long reference_combine(unsigned long lo
   return y;
 }
 
-// One output row per occupied slot whose reference partition matches.
+// Rows [min(groups, capacity), capacity) of every output column are zero after a finalize (include/qsx.h): the width of
+// aggregate a's value column, and one such row.
+__device__ __forceinline__ int out_value_width(const FinalizeDesc &f, int a) {
+  const bool typed = f.fn[a] == QSX_AGG_MIN || f.fn[a] == QSX_AGG_MAX;
+  return typed && (f.val_type[a] == QSX_INT || f.val_type[a] == QSX_FLOAT) ? 4 : 8;
+}
+__device__ __forceinline__ void zero_output_row(const FinalizeDesc &f, long long out_row) {
+  for (int k = 0; k < f.num_keys; ++k) {
+    switch (f.key_width[k]) {
+      case 1: static_cast<uint8_t *>(f.out_keys[k])[out_row] = 0; break;
+      case 2: static_cast<uint16_t *>(f.out_keys[k])[out_row] = 0; break;
+      case 4: static_cast<uint32_t *>(f.out_keys[k])[out_row] = 0; break;
+      default: static_cast<unsigned long long *>(f.out_keys[k])[out_row] = 0; break;
+    }
+  }
+  for (int a = 0; a < f.num_aggs; ++a) {
+    if (out_value_width(f, a) == 4) static_cast<uint32_t *>(f.out_vals[a])[out_row] = 0;
+    else static_cast<unsigned long long *>(f.out_vals[a])[out_row] = 0;
+    if (f.out_nulls[a] != nullptr) f.out_nulls[a][out_row] = 0;
+  }
+}
+// Behind the finalize kernels of a grid of workgroups (and alone, for a partition that holds nothing): the group count is
+// read on the device.  A count beyond the capacity — or QSX_GROUPS_HASH_COLLISION — leaves no tail.
+__global__ __launch_bounds__(kABlock) void finalize_tail_kernel(FinalizeDesc f, const unsigned long long *__restrict__ groups,
+                                                               long long capacity) {
+  const unsigned long long found = *groups;
+  const long long first = found < static_cast<unsigned long long>(capacity) ? static_cast<long long>(found) : capacity;
+  for (long long row = first + static_cast<long long>(blockIdx.x) * kABlock + threadIdx.x; row < capacity;
+       row += static_cast<long long>(gridDim.x) * kABlock) {
+    zero_output_row(f, row);
+  }
+}
+
+// Slot i of a hash-strategy table holds a group of finalize partition `partition` (code_out: its key code).
+__device__ __forceinline__ bool slot_emits(const HashTableView &g, const FinalizeDesc &f, unsigned long long i, int partition,
+                                           int num_partitions, int partition_by_hash, unsigned long long *code_out) {
+  const unsigned long long stride = g.cap + 1;
+  const unsigned long long code = i == g.cap ? kEmptyCode : g.keys[i];
+  *code_out = code;
+  const unsigned long long cnt = g.states[i];
+  bool emit = (i == g.cap) ? (cnt != 0) : (code != kEmptyCode);
+  if (emit && partition_by_hash) {
+    // partitioned aggregation routes a group to HashCompositeKey % P
+    // (storage/AggregationOperationState.cpp:576-583, utility/CompositeHash.hpp:39-48)
+    unsigned long long h = 0;
+    for (int k = 0; k < f.num_keys; ++k) {
+      unsigned long long bits = group_key_word(f, code, g.states, stride, i, f.key_word[k]) >> f.key_shift[k];
+      if (f.key_width[k] < 8) bits &= (1ull << (8 * f.key_width[k])) - 1;
+      const unsigned long long hk = reference_scalar_hash(f.key_type[k], bits);
+      h = k == 0 ? hk : reference_combine(h, hk);
+    }
+    emit = static_cast<int>(h % static_cast<unsigned long long>(num_partitions)) == partition;
+  }
+  return emit;
+}
+
+// The state's four control words into host-visible memory of the calling finalize (control_out, or nullptr): the host reads
+// them after its wait behind the kernel instead of copying them (qsx_agg_finalize).
+__device__ __forceinline__ void hand_control_words(const unsigned long long *control, unsigned long long *control_out) {
+  for (int w = 0; w < 4; ++w) __hip_atomic_store(&control_out[w], control[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// One output row per occupied slot whose reference partition matches.  out_groups is zero at the start.
 __global__ __launch_bounds__(kABlock) void finalize_hash_kernel(HashTableView g, FinalizeDesc f,
                                                                int partition, int num_partitions,
                                                                int partition_by_hash, long long capacity,
-                                                               unsigned long long *__restrict__ out_groups) {
+                                                               unsigned long long *__restrict__ out_groups,
+                                                               unsigned long long *control_out) {
+  if (control_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0) hand_control_words(g.ngroups, control_out);
   const unsigned long long stride = g.cap + 1;
   const unsigned long long total = g.cap + 1;
   const unsigned long long rounded = (total + kWave - 1) / kWave * kWave;
   for (unsigned long long i = static_cast<unsigned long long>(blockIdx.x) * kABlock + threadIdx.x;
        i < rounded; i += static_cast<unsigned long long>(gridDim.x) * kABlock) {
-    bool emit = false;
     unsigned long long code = kEmptyCode;
-    if (i < total) {
-      code = i == g.cap ? kEmptyCode : g.keys[i];
-      const unsigned long long cnt = g.states[i];
-      emit = (i == g.cap) ? (cnt != 0) : (code != kEmptyCode);
-      if (emit && partition_by_hash) {
-        // partitioned aggregation routes a group to HashCompositeKey % P
-        // (storage/AggregationOperationState.cpp:576-583, utility/CompositeHash.hpp:39-48)
-        unsigned long long h = 0;
-        for (int k = 0; k < f.num_keys; ++k) {
-          unsigned long long bits = group_key_word(f, code, g.states, stride, i, f.key_word[k]) >> f.key_shift[k];
-          if (f.key_width[k] < 8) bits &= (1ull << (8 * f.key_width[k])) - 1;
-          const unsigned long long hk = reference_scalar_hash(f.key_type[k], bits);
-          h = k == 0 ? hk : reference_combine(h, hk);
-        }
-        emit = static_cast<int>(h % static_cast<unsigned long long>(num_partitions)) == partition;
-      }
-    }
+    const bool emit = i < total && slot_emits(g, f, i, partition, num_partitions, partition_by_hash, &code);
     const uint64_t m = __ballot(emit);
     if (m == 0) continue;
     const int leader = __ffsll(static_cast<long long>(m)) - 1;
@@ -310,6 +404,44 @@ __global__ __launch_bounds__(kABlock) void finalize_hash_kernel(HashTableView g,
     write_keys_from_code(f, code, out_row, g.states, stride, i);
     write_values(f, g.states, stride, i, 0, false, out_row);
   }
+}
+
+// The same for a table and a capacity small enough for ONE workgroup: the groups are counted in LDS, so out_groups needs
+// no zeroing in front of the launch, and the workgroup zeroes the rows behind the groups itself.  kFinalizeBlockThreads
+// threads: the kernel is a chain of dependent loads per slot, so its time is the number of trips through the table.
+constexpr int kFinalizeBlockThreads = 1024;
+__global__ __launch_bounds__(kFinalizeBlockThreads) void finalize_hash_block_kernel(HashTableView g, FinalizeDesc f,
+                                                                     int partition, int num_partitions,
+                                                                     int partition_by_hash, long long capacity,
+                                                                     unsigned long long *__restrict__ out_groups,
+                                                                     unsigned long long *control_out) {
+  __shared__ unsigned long long s_groups;
+  if (threadIdx.x == 0) s_groups = 0;
+  if (control_out != nullptr && threadIdx.x == 0) hand_control_words(g.ngroups, control_out);
+  __syncthreads();
+  const unsigned long long stride = g.cap + 1;
+  const unsigned long long total = g.cap + 1;
+  const unsigned long long rounded = (total + kWave - 1) / kWave * kWave;
+  for (unsigned long long i = threadIdx.x; i < rounded; i += kFinalizeBlockThreads) {
+    unsigned long long code = kEmptyCode;
+    const bool emit = i < total && slot_emits(g, f, i, partition, num_partitions, partition_by_hash, &code);
+    const uint64_t m = __ballot(emit);
+    if (m == 0) continue;
+    const int leader = __ffsll(static_cast<long long>(m)) - 1;
+    unsigned long long base = 0;
+    if (lane_id() == leader) base = atomicAdd(&s_groups, static_cast<unsigned long long>(__popcll(m)));
+    base = __shfl(base, leader, kWave);
+    if (!emit) continue;
+    const long long out_row = static_cast<long long>(base) + rank_below(m);
+    if (out_row >= capacity) continue;
+    write_keys_from_code(f, code, out_row, g.states, stride, i);
+    write_values(f, g.states, stride, i, 0, false, out_row);
+  }
+  __syncthreads();
+  const unsigned long long found = s_groups;
+  if (threadIdx.x == 0) *out_groups = found;
+  const long long first = found < static_cast<unsigned long long>(capacity) ? static_cast<long long>(found) : capacity;
+  for (long long row = first + threadIdx.x; row < capacity; row += kFinalizeBlockThreads) zero_output_row(f, row);
 }
 
 // ---- K11 standalone: a scalar expression projected into a column (qsx_eval_expression) --------------------------------
@@ -2066,11 +2198,51 @@ int qsx_agg_state_destroy(qsx_agg_state_t *st) {
   return QSX_OK;
 }
 
+}  // extern "C"
+
+// Hash-strategy states of at most this many 8-byte words (table image + directory) are cleared by clear_hash_state_kernel
+// in one launch.  Measured (profiles/clear_threshold.jsonl, DESIGN.md §4 "The small launches of a step"): the five memsets
+// are launch-bound at 22 us up to 2 Mi words, where the kernel takes 7-8 us; at 8 Mi words 26 against 13 us, at 32 Mi words
+// 60 against 42 us.  No size measured favours the memsets; nothing larger was measured, so above 32 Mi words (256 MiB) —
+// and for dense images — they stay.  QSX_AGG_CLEAR_ONE_KERNEL_WORDS, read per call, moves the threshold: the tests clear
+// the same state through both paths.
+static unsigned long long clear_one_kernel_max_words() {
+  const char *e = getenv("QSX_AGG_CLEAR_ONE_KERNEL_WORDS");
+  return e != nullptr ? static_cast<unsigned long long>(atoll(e)) : 1ull << 25;
+}
+
+extern "C" {
+
 int qsx_agg_state_clear(qsx_agg_state_t *st, qsx_stream_t stream) {
   QSX_REQUIRE_DEVICE();
   if (st == nullptr) return QSX_ERR_INVALID_ARGUMENT;
   hipStream_t s = as_stream(stream);
   std::unique_lock<std::shared_mutex> lock(st->table_mutex);
+  if (!st->dense) {
+    const unsigned long long dir_words = st->dir_gids != 0 ? st->dir_cap * st->dir_entry_words : 0ull;
+    const unsigned long long words = (st->cap + 1) * (st->num_cols + 1) + dir_words;
+    if (words <= clear_one_kernel_max_words()) {
+      ClearDesc c{};
+      c.image = st->image;
+      c.slots = st->cap + 1;
+      c.num_cols = st->num_cols;
+      c.kinds = st->col_kinds;
+      c.dir_entries = st->dir_gids != 0 ? st->dir_entries : nullptr;
+      c.dir_words = dir_words;
+      c.dir_ngids = st->dir_ngids;
+      c.log = st->growable ? st->log : nullptr;
+      c.log_stride = st->num_cols + 1;
+      c.log_cap = kLogRecords;
+      c.control = st->control;
+      hipLaunchKernelGGL(clear_hash_state_kernel, dim3(grid_for(static_cast<int64_t>(words), kABlock * 4)), dim3(kABlock), 0, s, c);
+      QSX_CHECK_LAUNCH();
+      if (st->growable) {
+        __atomic_store_n(&st->published[0], 0ull, __ATOMIC_RELEASE);
+        __atomic_store_n(&st->published[1], 0ull, __ATOMIC_RELEASE);
+      }
+      return QSX_OK;
+    }
+  }
   if (st->growable) {
     // records a previous run left in the spill log go back to their identities (before the count is zeroed below)
     int rc = init_log(st, st->log, 0, reinterpret_cast<const unsigned int *>(st->control + 3), s);
@@ -3874,51 +4046,64 @@ int qsx_eval_expression_long(int num_columns, const void *const *cols, const int
   return QSX_OK;
 }
 
-int qsx_agg_finalize(qsx_agg_state_t *st, int partition, int num_partitions, void *const *out_key_cols,
-                     void *const *out_val_cols, uint8_t *const *out_null_cols, int64_t capacity,
-                     int64_t *out_groups_dev, qsx_stream_t stream) {
-  QSX_REQUIRE_DEVICE();
-  if (st == nullptr || out_groups_dev == nullptr || num_partitions < 1 || partition < 0 ||
-      partition >= num_partitions || capacity < 0 || out_val_cols == nullptr) {
-    return QSX_ERR_INVALID_ARGUMENT;
+}  // extern "C"
+
+// Tables of at most this many slots, finalized into at most this many rows, take finalize_hash_block_kernel.
+constexpr unsigned long long kFinalizeBlockSlots = 8192;
+constexpr int64_t kFinalizeBlockRows = 8192;
+
+// Four host-visible words for the length of one call (a slot of the pool the published control words come from).
+struct CallControlWords {
+  unsigned long long *host = published_slots().take();
+  unsigned long long *dev = nullptr;
+  CallControlWords() {
+    if (host != nullptr && hipHostGetDevicePointer(reinterpret_cast<void **>(&dev), host, 0) != hipSuccess) {
+      (void)hipGetLastError();
+      dev = nullptr;
+    }
   }
-  hipStream_t s = as_stream(stream);
-  int rc = settle(st, s);
-  if (rc != QSX_OK) return rc;
-  std::shared_lock<std::shared_mutex> lock(st->table_mutex);
-  FinalizeDesc f = st->fin;
-  for (int k = 0; k < f.num_keys; ++k) {
-    if (out_key_cols == nullptr || out_key_cols[k] == nullptr) return QSX_ERR_INVALID_ARGUMENT;
-    f.out_keys[k] = out_key_cols[k];
-  }
-  for (int a = 0; a < f.num_aggs; ++a) {
-    f.out_vals[a] = out_val_cols[a];
-    f.out_nulls[a] = out_null_cols != nullptr ? out_null_cols[a] : nullptr;
-  }
+  ~CallControlWords() { published_slots().give(host); }
+  CallControlWords(const CallControlWords &) = delete;
+  CallControlWords &operator=(const CallControlWords &) = delete;
+};
+
+// Enqueues one finalize of partition `partition` over the table as it is now, the zeroing of the rows behind the groups
+// included.  Caller holds table_mutex (shared).
+// control_out (or nullptr): host-visible words of this call; *handed = a kernel of this launch writes the control words there.
+static int launch_finalize(qsx_agg_state *st, const FinalizeDesc &f, int partition, int num_partitions, int64_t capacity,
+                           int64_t *out_groups_dev, hipStream_t s, unsigned long long *control_out, bool *handed) {
+  *handed = false;
   unsigned long long *out_groups = reinterpret_cast<unsigned long long *>(out_groups_dev);
-  QSX_HIP_TRY(hipMemsetAsync(out_groups_dev, 0, sizeof(int64_t), s));
-  f.collision = reinterpret_cast<int *>(st->control + 4);
+  bool tail_done = false;   // the kernel zeroed rows [groups, capacity) itself
+  bool emits = true;        // false: this partition holds nothing by construction — zero groups, every row zero
   switch (st->config.strategy) {
     case QSX_AGG_SINGLE_STATE:
-      if (partition != 0) return QSX_OK;
+      if (partition != 0) { emits = false; break; }
       if (capacity < 1) return QSX_ERR_CAPACITY;
       hipLaunchKernelGGL(finalize_single_kernel, dim3(1), dim3(64), 0, s, st->hash_view(), f, out_groups);
       break;
     case QSX_AGG_COMPACT_KEY:
+    case QSX_AGG_GENERIC: {
       // compact-key tables are finalized in one piece (AggregationOperationState.cpp:925-948)
-      if (partition != 0) return QSX_OK;
-      hipLaunchKernelGGL(finalize_hash_kernel, dim3(grid_for(st->cap + 1, kABlock)), dim3(kABlock), 0, s,
-                         st->hash_view(), f, 0, 1, 0, static_cast<long long>(capacity), out_groups);
+      const bool generic = st->config.strategy == QSX_AGG_GENERIC;
+      if (!generic && partition != 0) { emits = false; break; }
+      if (st->cap + 1 <= kFinalizeBlockSlots && capacity <= kFinalizeBlockRows) {
+        hipLaunchKernelGGL(finalize_hash_block_kernel, dim3(1), dim3(kFinalizeBlockThreads), 0, s, st->hash_view(), f, generic ? partition : 0,
+                           generic ? num_partitions : 1, generic ? 1 : 0, static_cast<long long>(capacity), out_groups, control_out);
+        tail_done = true;
+      } else {
+        QSX_HIP_TRY(hipMemsetAsync(out_groups_dev, 0, sizeof(int64_t), s));
+        hipLaunchKernelGGL(finalize_hash_kernel, dim3(grid_for(st->cap + 1, kABlock)), dim3(kABlock), 0, s, st->hash_view(), f,
+                           generic ? partition : 0, generic ? num_partitions : 1, generic ? 1 : 0, static_cast<long long>(capacity),
+                           out_groups, control_out);
+      }
+      *handed = control_out != nullptr;
       break;
-    case QSX_AGG_GENERIC:
-      hipLaunchKernelGGL(finalize_hash_kernel, dim3(grid_for(st->cap + 1, kABlock)), dim3(kABlock), 0, s,
-                         st->hash_view(), f, partition, num_partitions, 1, static_cast<long long>(capacity),
-                         out_groups);
-      break;
+    }
     default: {
       const DenseRange range = dense_partition_range(st->config.num_entries, num_partitions, partition);
       const long long begin = range.begin, end = range.end;
-      if (begin >= end) return QSX_OK;
+      if (begin >= end) { emits = false; break; }
       const long long first_word = range.first_word;
       const long long num_words = range.last_word - first_word;
       const long long num_tiles = (num_words + kDenseTileWords - 1) / kDenseTileWords;
@@ -3936,6 +4121,7 @@ int qsx_agg_finalize(qsx_agg_state_t *st, int partition, int num_partitions, voi
       hipLaunchKernelGGL(dense_tile_count_kernel, dim3(grid_for(num_tiles, kABlock / kWave)), dim3(kABlock), 0, s,
                          d.exist, first_word, num_words, begin, end, num_tiles, tile_counts);
       QSX_CHECK_LAUNCH();
+      // (the scan writes the group count: nothing to zero in front of it)
       hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, s, tile_counts,
                          static_cast<int64_t>(num_tiles), tile_offsets, out_groups_dev);
       QSX_CHECK_LAUNCH();
@@ -3945,12 +4131,80 @@ int qsx_agg_finalize(qsx_agg_state_t *st, int partition, int num_partitions, voi
       break;
     }
   }
-  QSX_CHECK_LAUNCH();
-  if (f.wide_words != 0) {
+  if (emits) QSX_CHECK_LAUNCH();
+  else QSX_HIP_TRY(hipMemsetAsync(out_groups_dev, 0, sizeof(int64_t), s));
+  if (!tail_done && capacity > 0) {
+    hipLaunchKernelGGL(finalize_tail_kernel, dim3(grid_for(capacity, kABlock)), dim3(kABlock), 0, s, f, out_groups,
+                       static_cast<long long>(capacity));
+    QSX_CHECK_LAUNCH();
+  }
+  if (emits && f.wide_words != 0) {
     hipLaunchKernelGGL(report_collision_kernel, dim3(1), dim3(64), 0, s, f.collision, out_groups);
     QSX_CHECK_LAUNCH();
   }
   return QSX_OK;
+}
+
+extern "C" {
+
+// The finalize is enqueued BEFORE the host waits for the stream: the wait that tells whether the table is at rest (no
+// lost rows, nothing in the spill log, load <= 1/4) then covers the finalize kernel as well, instead of the device idling
+// between the wait and a launch behind it.  Normally the table was at rest and the outputs stand; a table that has to grow
+// is finalized a second time over the grown table.
+int qsx_agg_finalize(qsx_agg_state_t *st, int partition, int num_partitions, void *const *out_key_cols,
+                     void *const *out_val_cols, uint8_t *const *out_null_cols, int64_t capacity,
+                     int64_t *out_groups_dev, qsx_stream_t stream) {
+  QSX_REQUIRE_DEVICE();
+  if (st == nullptr || out_groups_dev == nullptr || num_partitions < 1 || partition < 0 ||
+      partition >= num_partitions || capacity < 0 || out_val_cols == nullptr) {
+    return QSX_ERR_INVALID_ARGUMENT;
+  }
+  hipStream_t s = as_stream(stream);
+  FinalizeDesc f = st->fin;
+  bool valid = true;
+  for (int k = 0; k < f.num_keys; ++k) {
+    valid = valid && out_key_cols != nullptr && out_key_cols[k] != nullptr;
+    if (valid) f.out_keys[k] = out_key_cols[k];
+  }
+  for (int a = 0; a < f.num_aggs; ++a) {
+    f.out_vals[a] = out_val_cols[a];
+    f.out_nulls[a] = out_null_cols != nullptr ? out_null_cols[a] : nullptr;
+  }
+  f.collision = reinterpret_cast<int *>(st->control + 4);
+  // What settle() does, behind the finalize.  The hash-strategy kernels hand the control words over themselves, into
+  // host-visible words that belong to this call; the other strategies' are copied.  Not published[]: that slot is the
+  // state's, and a finalize of another partition that grows the table meanwhile (grow_and_drain stores the grown table's
+  // words there) would make this call believe its own kernel — which ran over the table before it grew — saw a table at
+  // rest.  Kernel and copy are enqueued under one lock, so both see the table on the same side of a growth.
+  CallControlWords words;
+  int launched = QSX_ERR_INVALID_ARGUMENT;
+  unsigned long long control[4] = {0, 0, 0, 0};
+  bool handed = false;
+  {
+    std::shared_lock<std::shared_mutex> lock(st->table_mutex);
+    if (valid) launched = launch_finalize(st, f, partition, num_partitions, capacity, out_groups_dev, s, words.dev, &handed);
+    if (launched != QSX_OK) handed = false;
+    if (!handed) QSX_HIP_TRY(hipMemcpyAsync(control, st->control, sizeof(control), hipMemcpyDeviceToHost, s));
+  }
+  QSX_HIP_TRY(hipStreamSynchronize(s));
+  if (handed) {
+    for (int w = 0; w < 4; ++w) control[w] = __atomic_load_n(&words.host[w], __ATOMIC_ACQUIRE);
+  }
+  if (static_cast<int>(control[1] & 0xFFFFFFFFu) != 0) {
+    return st->dense ? QSX_ERR_INVALID_ARGUMENT : QSX_ERR_TOO_MANY_GROUPS;
+  }
+  if (st->growable && ((control[3] & 0xFFFFFFFFull) != 0 || control[0] * 4 > st->cap)) {
+    {
+      std::unique_lock<std::shared_mutex> lock(st->table_mutex);
+      const int rc = grow_and_drain(st);
+      if (rc != QSX_OK) return rc;
+    }
+    if (launched != QSX_OK) return launched;
+    std::shared_lock<std::shared_mutex> lock(st->table_mutex);
+    launched = launch_finalize(st, f, partition, num_partitions, capacity, out_groups_dev, s, nullptr, &handed);
+    if (launched == QSX_OK) QSX_HIP_TRY(hipStreamSynchronize(s));
+  }
+  return launched;
 }
 
 }  // extern "C"

@@ -353,8 +353,11 @@ __global__ __launch_bounds__(kJBlock) void compact_build_kernel(TableView t, uin
 }
 
 // head[] -> the 3-byte copy the probes read (sealed_pack).  Entries beyond 23 bits cannot occur: the host checks the row
-// and overflow counts first.
-__global__ __launch_bounds__(kJBlock) void dense_pack_kernel(const uint32_t *__restrict__ head, uint64_t range, unsigned char *__restrict__ head3) {
+// and overflow counts first.  count_word (or nullptr): the pair counter of the probe this pack was launched for, zeroed here
+// instead of by a memset of its own.
+__global__ __launch_bounds__(kJBlock) void dense_pack_kernel(const uint32_t *__restrict__ head, uint64_t range, unsigned char *__restrict__ head3,
+                                                             unsigned long long *count_word) {
+  if (count_word != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *count_word = 0ull;
   for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kJBlock + threadIdx.x; i < range; i += static_cast<uint64_t>(gridDim.x) * kJBlock) {
     const uint32_t w = head[i];
     const uint32_t packed = (w & 0x7FFFFFu) | ((w & kChainBit) >> 8);
@@ -362,6 +365,20 @@ __global__ __launch_bounds__(kJBlock) void dense_pack_kernel(const uint32_t *__r
     head3[i * 3 + 1] = static_cast<unsigned char>(packed >> 8);
     head3[i * 3 + 2] = static_cast<unsigned char>(packed >> 16);
   }
+}
+
+// qsx_join_table_clear of a directly addressed table in one launch: head[] (16 bytes per store, the allocation is aligned) and
+// the control words.
+__global__ __launch_bounds__(kJBlock) void dense_clear_kernel(uint32_t *__restrict__ head, uint64_t range, unsigned long long *__restrict__ control,
+                                                              int control_words) {
+  const uint64_t quads = range / 4;
+  uint4 *head4 = reinterpret_cast<uint4 *>(head);
+  for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kJBlock + threadIdx.x; i < quads; i += static_cast<uint64_t>(gridDim.x) * kJBlock) {
+    head4[i] = make_uint4(0u, 0u, 0u, 0u);
+  }
+  if (blockIdx.x != 0) return;
+  if (threadIdx.x < range - quads * 4) head[quads * 4 + threadIdx.x] = 0u;
+  for (int w = threadIdx.x; w < control_words; w += kJBlock) control[w] = 0ull;
 }
 
 // Every entry of a hashed table into a directly addressed one (seal_table): what dense_build_kernel does per build row.
@@ -1259,13 +1276,15 @@ int qsx_join_table_clear(qsx_join_table_t *t, qsx_stream_t stream) {
   if (t == nullptr) return QSX_ERR_INVALID_ARGUMENT;
   std::unique_lock<std::shared_mutex> lock(t->mutex);
   if (t->dense) {
-    QSX_HIP_TRY(hipMemsetAsync(t->head, 0, t->range * sizeof(uint32_t), as_stream(stream)));
+    hipLaunchKernelGGL(dense_clear_kernel, dim3(grid_for(static_cast<int64_t>(t->range / 4), kJBlock * 4)), dim3(kJBlock), 0, as_stream(stream),
+                       t->head, t->range, t->entries_dev, static_cast<int>(kControlBytes / sizeof(unsigned long long)));
+    QSX_CHECK_LAUNCH();
   } else {
     const int rc_fill = fill_empty(t, t->slots, t->capacity, as_stream(stream));
     if (rc_fill != QSX_OK) return rc_fill;
+    const int rc_control = reset_control_words(t->entries_dev, as_stream(stream));
+    if (rc_control != QSX_OK) return rc_control;
   }
-  const int rc_control = reset_control_words(t->entries_dev, as_stream(stream));
-  if (rc_control != QSX_OK) return rc_control;
   t->reserved = 0;
   t->max_tid.store(-1);
   t->seal_state.store(0);
@@ -1458,8 +1477,9 @@ static bool adaptive_enabled() {
 
 // Directly addressed tables around the size of an XCD's L2: the first probe after the builds packs head[] to 3 bytes per key
 // value when that makes it fit (4-byte words beyond ~3.25 MiB, the packed copy at most 3.6 MiB, every stored number below
-// 2^23).  Builds keep working on head[]; a build or clear drops the copy.
-static void sealed_pack(qsx_join_table *t, hipStream_t stream) {
+// 2^23).  Builds keep working on head[]; a build or clear drops the copy.  count_word: the calling probe's pair counter; true
+// is returned when this call launched the pack kernel and the kernel zeroes the counter (else the caller does).
+static bool sealed_pack(qsx_join_table *t, hipStream_t stream, unsigned long long *count_word = nullptr) {
   // packed on another stream a moment ago?  This stream's probe must not overtake the pack kernel.
   auto behind_the_pack = [&]() {
     if (t->pack_stream != stream && t->pack_event != nullptr && hipEventQuery(t->pack_event) != hipSuccess) {
@@ -1470,13 +1490,13 @@ static void sealed_pack(qsx_join_table *t, hipStream_t stream) {
   int state = t->seal_state.load(std::memory_order_acquire);
   if (state == 2) {
     behind_the_pack();
-    return;
+    return false;
   }
-  if (state != 0 || !adaptive_enabled()) return;
+  if (state != 0 || !adaptive_enabled()) return false;
   const uint64_t bytes4 = t->range * 4, bytes3 = t->range * 3;
   // every number a head word can hold — tuple id + 1, overflow entry — stays below 2^23: both bounds are known on the host
   if (bytes4 <= (13ull << 18) || bytes3 > (36ull << 20) / 10 || t->max_tid.load() >= (1 << 23) - 2 || t->reserved >= (1 << 23) - 1) {
-    return;   // (not marked: the test is four comparisons)
+    return false;   // (not marked: the test is four comparisons)
   }
   std::lock_guard<std::mutex> lock(t->seal_mutex);
   state = t->seal_state.load(std::memory_order_acquire);
@@ -1485,7 +1505,7 @@ static void sealed_pack(qsx_join_table *t, hipStream_t stream) {
     // thread's probe is about to read head3 (a probe that overtook the pack found zeros: 2.6 % of a join's rows lost once in
     // ~20 runs of 20 concurrent single-block work orders, tests/test_host_layer.py)
     if (state == 2) behind_the_pack();
-    return;
+    return false;
   }
   // No host synchronisation: the pack kernel is ordered on the probing stream behind the builds the caller has ordered
   // before this probe (pipeline breaker), and other streams' probes wait for its event.
@@ -1493,24 +1513,25 @@ static void sealed_pack(qsx_join_table *t, hipStream_t stream) {
     (void)hipGetLastError();
     t->head3 = nullptr;
     t->seal_state.store(1, std::memory_order_release);
-    return;
+    return false;
   }
   if (t->pack_event == nullptr && hipEventCreateWithFlags(&t->pack_event, hipEventDisableTiming) != hipSuccess) {
     (void)hipGetLastError();
     t->pack_event = nullptr;
     t->seal_state.store(1, std::memory_order_release);
-    return;
+    return false;
   }
   hipLaunchKernelGGL(dense_pack_kernel, dim3(grid_for(static_cast<int64_t>(t->range), kJBlock * 4)), dim3(kJBlock), 0, stream, t->head, t->range,
-                     t->head3);
+                     t->head3, count_word);
   if (hipGetLastError() != hipSuccess || hipEventRecord(t->pack_event, stream) != hipSuccess) {
     (void)hipGetLastError();
     (void)hipStreamSynchronize(stream);
     t->seal_state.store(1, std::memory_order_release);
-    return;
+    return false;
   }
   t->pack_stream = stream;
   t->seal_state.store(2, std::memory_order_release);
+  return count_word != nullptr;
 }
 
 static bool compact_enabled() {
@@ -1772,9 +1793,10 @@ static int launch_probe(qsx_join_table_t *t, const void *keys, int64_t n, int32_
       return QSX_ERR_HIP;
     }
   }
-  if (out_count != nullptr) QSX_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(int64_t), stream));
+  // (a table that is packed in this call has the pack kernel zero the counter)
+  const bool zeroed = n != 0 && t->dense && sealed_pack(t, stream, reinterpret_cast<unsigned long long *>(out_count));
+  if (out_count != nullptr && !zeroed) QSX_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(int64_t), stream));
   if (n == 0) return QSX_OK;
-  if (t->dense) sealed_pack(t, stream);
   std::shared_lock<std::shared_mutex> lock(t->mutex);
   if (t->dense) {
     const int64_t tiles = kRuns ? run_tiles : (n + kDenseTile - 1) / kDenseTile;

@@ -814,6 +814,59 @@ int qsx_eval_expression_long(int num_columns, const void *const *cols, const int
                              const qsx_expr_instr_t *instrs, const int64_t *consts, qsx_operand_t result, int64_t n, int out_width,
                              void *out_dev, qsx_stream_t stream);
 
+/* Searched CASE: out[i] = the value of the first WHEN that holds at row i, else the ELSE value — what
+ * ScalarCaseExpression::getAllValues computes per block (expressions/scalar/ScalarCaseExpression.cpp:273-350: a
+ * TupleIdSequence per WHEN over the rows no earlier WHEN took, every result expression materialised over its own matches,
+ * MultiplexNativeColumnVector scattering the pieces into one column), in ONE pass over the WHEN bitmaps the select kernels
+ * wrote.  The projection of a CASE by a SelectWorkOrder and the argument of SUM(CASE WHEN .. THEN .. ELSE .. END)
+ * (TPC-H Q8, Q12, Q14) come here; QSX_ABI_VERSION did not change: a caller detects the capability by the presence of the
+ * symbols.
+ *   Selection  row i takes branch k, the smallest k with bit i of when_bitmaps_dev[k] set; no bit set: ELSE.  The bitmaps are
+ *              TupleIdSequence-compatible as every qsx_select_* writes them (device pointers in a HOST array of num_whens
+ *              entries) and may overlap.  A comparison with a NULL is already "not true" in them.
+ *   Value      all branch values come from one shared program of qsx_expr_instr_t under the rules above: double ops, and
+ *              QSX_EX_IADD .. IDIV in integer arithmetic (INT wraps to 32 bits, x / 0 = 0, x / -1 = 0 - x); a double
+ *              instruction may read an integer temp; a subexpression two branches share is computed once.  value[k] is
+ *              the THEN of WHEN k, value[num_whens] the ELSE: a COLUMN, a CONST (an INT when consts[] holds an integral value
+ *              that fits 32 bits, a LONG when it is integral with |c| <= 2^53, else a DOUBLE), a TEMP, or QSX_OPD_NULL, the NULL
+ *              literal (an absent ELSE).  The chosen operand is converted to out_type at the store — the resolver's Cast
+ *              to the branches' unified type (query_optimizer/resolver/Resolver.cpp:2819-2829): INT -> LONG sign-extends,
+ *              INT / LONG / FLOAT -> DOUBLE converts.  Every node is rounded on its own, like qsx_eval_expression.
+ *   NULL       row i is NULL when its chosen branch is QSX_OPD_NULL, or when a column that branch's value depends on
+ *              (through temps: a temp is NULL when any operand is) is NULL at i — col_null_bitmaps: NULL, or a host array of
+ *              num_columns device bitmaps (entries may be NULL), bit set = NULL.  NULLs in columns only unchosen branches read
+ *              do not count (the reference evaluates a result expression over its own matches only).  A NULL row stores 0 and
+ *              sets its bit in out_null_bitmap_dev, whose (n + 63) / 64 words are written in full (bits >= n are 0).
+ *              out_null_bitmap_dev may be NULL only when no branch is QSX_OPD_NULL and col_null_bitmaps is NULL.
+ *   Unchosen   branches may be evaluated (no op traps); their values are never stored.
+ *   out_dev    n values of out_type: QSX_INT (4 bytes), QSX_LONG or QSX_DOUBLE.
+ * QSX_ERR_INVALID_ARGUMENT: num_whens outside 1 .. QSX_MAX_CASE_WHENS; an out_type outside the three; an integer out_type with
+ * a branch that is a double temp, a FLOAT / DOUBLE column or a non-integral constant; out_type INT with a LONG branch; a
+ * QSX_OPD_NULL anywhere but in value[]; an operand index out of range or a temp read before it is written; a missing
+ * out_null_bitmap_dev; NULL pointers with n > 0.  A CHAR / DATE column: QSX_ERR_UNSUPPORTED.  Without a device:
+ * QSX_ERR_NO_DEVICE, in front of everything. */
+#define QSX_MAX_CASE_WHENS 8
+#define QSX_OPD_NULL 3            /* only as a branch value of qsx_eval_case: the NULL literal */
+typedef struct qsx_case_desc {
+  int32_t num_whens;                              /* 1 .. QSX_MAX_CASE_WHENS */
+  qsx_operand_t value[QSX_MAX_CASE_WHENS + 1];    /* value[k]: THEN of WHEN k; value[num_whens]: ELSE */
+  int32_t out_type;                               /* QSX_INT (4 bytes) / QSX_LONG / QSX_DOUBLE */
+} qsx_case_desc_t;
+size_t qsx_abi_sizeof_case_desc(void);
+int qsx_eval_case(int num_columns, const void *const *cols, const int32_t *types, const uint64_t *const *col_null_bitmaps,
+                  int num_instrs, const qsx_expr_instr_t *instrs, const double *consts, const qsx_case_desc_t *desc,
+                  const uint64_t *const *when_bitmaps_dev, int64_t n, void *out_dev, uint64_t *out_null_bitmap_dev,
+                  qsx_stream_t stream);
+/* The same program and desc over a run of blocks in one launch, every block with its own stripes and bitmaps (host arrays of
+ * device pointers): block_cols[b * num_columns + c], block_col_null_bitmaps (NULL, or the same indexing with NULL entries
+ * allowed), block_when_bitmaps[b * num_whens + k], block_out[b], block_out_null_bitmaps[b] (NULL under the rule above).  Every
+ * block's output and null bitmap are those of qsx_eval_case on that block alone, byte for byte. */
+int qsx_eval_case_blocks(int num_columns, const int32_t *types, int num_instrs, const qsx_expr_instr_t *instrs,
+                         const double *consts, const qsx_case_desc_t *desc, int64_t num_blocks, const int64_t *block_rows,
+                         const void *const *block_cols, const uint64_t *const *block_col_null_bitmaps,
+                         const uint64_t *const *block_when_bitmaps, void *const *block_out,
+                         uint64_t *const *block_out_null_bitmaps, qsx_stream_t stream);
+
 typedef struct qsx_agg_config {
   int32_t strategy;                       /* qsx_agg_strategy_t */
   int32_t num_columns;                    /* columns handed to every qsx_agg_update */

@@ -127,6 +127,11 @@ _SIGNATURES = {
     "qsx_join_probe_exists": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _vp, _vp]),
     "qsx_eval_expression": (_int, [_int, _pp, C.POINTER(_i32), _int, C.POINTER(T.ExprInstr), C.POINTER(C.c_double), T.Operand, _i64, _vp, _vp]),
     "qsx_eval_expression_long": (_int, [_int, _pp, C.POINTER(_i32), _int, C.POINTER(T.ExprInstr), C.POINTER(_i64), T.Operand, _i64, _int, _vp, _vp]),
+    "qsx_abi_sizeof_case_desc": (_sz, []),
+    "qsx_eval_case": (_int, [_int, _pp, C.POINTER(_i32), _pp, _int, C.POINTER(T.ExprInstr), C.POINTER(C.c_double), C.POINTER(T.CaseDesc), _pp,
+                             _i64, _vp, _vp, _vp]),
+    "qsx_eval_case_blocks": (_int, [_int, C.POINTER(_i32), _int, C.POINTER(T.ExprInstr), C.POINTER(C.c_double), C.POINTER(T.CaseDesc), _i64,
+                                    C.POINTER(_i64), _pp, _pp, _pp, _pp, _pp, _vp]),
     "qsx_agg_state_create": (_int, [C.POINTER(T.AggConfig), _pp]),
     "qsx_agg_state_destroy": (_int, [_vp]),
     "qsx_select_cmp_sorted_blocks": (_int, [_int, _i64, C.POINTER(_i64), _pp, _int, _vp, _pp, _pp, _vp, _vp]),
@@ -196,6 +201,9 @@ if _lib.qsx_abi_sizeof_agg_config() != C.sizeof(T.AggConfig):
 
 if _lib.qsx_abi_sizeof_sort_key() != C.sizeof(T.SortKey):
     raise ImportError("quickstep_amd.types.SortKey does not match qsx_sort_key_t of libqsx.so")
+
+if _lib.qsx_abi_sizeof_case_desc() != C.sizeof(T.CaseDesc):
+    raise ImportError("quickstep_amd.types.CaseDesc does not match qsx_case_desc_t of libqsx.so")
 
 lib = _lib
 EXPORTED = tuple(_SIGNATURES)
@@ -543,6 +551,53 @@ def eval_expression_long(cols, instrs, consts, result, out_dtype=torch.int64, st
     _check(_lib.qsx_eval_expression_long(len(cols), ptrs, types, len(instrs), prog, cs, result, n, out.element_size(), _ptr(out),
                                          _stream(stream)), "qsx_eval_expression_long")
     return out
+
+
+_CASE_DTYPE = {T.INT: torch.int32, T.LONG: torch.int64, T.DOUBLE: torch.float64}
+
+
+def _case_program(cols, instrs, consts, values, out_type):
+    types = (C.c_int32 * max(len(cols), 1))(*[qsx_type_of(c) for c in cols])
+    prog = (T.ExprInstr * max(len(instrs), 1))(*[T.ExprInstr(op, dst, a, b) for op, dst, a, b in instrs])
+    cs = (C.c_double * T.MAX_CONSTS)(*list(consts))
+    return types, prog, cs, T.make_case_desc(values, out_type)
+
+
+def eval_case(cols, instrs, consts, values, whens, out_type, col_nulls=None, want_nulls=True, n=None, stream=None, out=None, out_nulls=None):
+    """Searched CASE (qsx_eval_case): whens = the WHEN bitmaps in order (the first set bit wins), values = the THEN operand
+    of every WHEN and then the ELSE operand (T.col / T.const / T.temp / T.null) over one shared program, out_type T.INT /
+    T.LONG / T.DOUBLE.  col_nulls: None, or one entry per column (a null bitmap, bit set = NULL, or None).  Returns
+    (values, null bitmap); the bitmap is None without want_nulls.  out / out_nulls: tensors to write into.  n: the number of rows;
+    it must be given for a CASE over no columns (constant and NULL branches only)."""
+    n = cols[0].numel() if n is None else n
+    device = cols[0].device if cols else whens[0].device
+    if out is None:
+        out = torch.empty(n, dtype=_CASE_DTYPE.get(out_type, torch.float64), device=device)
+    if out_nulls is None and want_nulls:
+        out_nulls = new_bitmap(n, device)
+    types, prog, cs, desc = _case_program(cols, instrs, consts, values, out_type)
+    _check(_lib.qsx_eval_case(len(cols), _ptr_array(cols), types, None if col_nulls is None else _ptr_array(col_nulls), len(instrs), prog, cs,
+                              C.byref(desc), _ptr_array(whens), n, _ptr(out), _ptr(out_nulls), _stream(stream)), "qsx_eval_case")
+    return out, out_nulls
+
+
+def eval_case_blocks(blocks, instrs, consts, values, block_whens, out_type, block_col_nulls=None, want_nulls=True, stream=None, rows=None):
+    """eval_case over a run of blocks in one launch (qsx_eval_case_blocks): blocks = one list of column stripes per block,
+    block_whens = one list of WHEN bitmaps per block, block_col_nulls = None or one list (bitmap or None per column) per block.
+    rows: every block's number of rows; it must be given for a CASE over no columns.  Returns (list of value tensors, list of null
+    bitmaps or None)."""
+    nb = len(blocks)
+    device = block_whens[0][0].device
+    counts = [b[0].numel() for b in blocks] if rows is None else [int(r) for r in rows]
+    rows = (C.c_int64 * max(nb, 1))(*counts)
+    outs = [torch.empty(r, dtype=_CASE_DTYPE.get(out_type, torch.float64), device=device) for r in counts]
+    out_nulls = [new_bitmap(r, device) for r in counts] if want_nulls else None
+    types, prog, cs, desc = _case_program(blocks[0], instrs, consts, values, out_type)
+    flat = lambda lists: _ptr_array([t for one in lists for t in one])   # noqa: E731
+    _check(_lib.qsx_eval_case_blocks(len(blocks[0]), types, len(instrs), prog, cs, C.byref(desc), nb, rows, flat(blocks),
+                                     None if block_col_nulls is None else flat(block_col_nulls), flat(block_whens), _ptr_array(outs),
+                                     None if out_nulls is None else _ptr_array(out_nulls), _stream(stream)), "qsx_eval_case_blocks")
+    return outs, out_nulls
 
 
 def select_codes_sorted(codes, op, first, second=0, filter_bitmap=None, stream=None):

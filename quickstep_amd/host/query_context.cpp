@@ -532,6 +532,22 @@ TypeID ScalarResultType(const ScalarPtr &scalar, const CatalogRelation &relation
     }
     case Scalar::kLiteral:
       return scalar->literal_type;
+    case Scalar::kCaseExpression: {
+      // the unifying type of the branches (Resolver.cpp:2819-2829); a NULL branch has no say
+      TypeID unified = kInt;
+      bool any = false;
+      const auto take = [&](const ScalarPtr &branch) {
+        if (branch == nullptr) return;
+        const TypeID t = ScalarResultType(branch, relation);
+        any = true;
+        if (t == kDouble || unified == kDouble) unified = kDouble;
+        else if (t == kLong) unified = kLong;
+      };
+      for (const auto &when : scalar->whens) take(when.second);
+      take(scalar->else_result);
+      if (!any) throw ExecutionError("CASE: every branch is NULL", QSX_ERR_UNSUPPORTED);
+      return unified;
+    }
     default: {
       const TypeID l = ScalarResultType(scalar->left, relation), r = ScalarResultType(scalar->right, relation);
       if (l == kDouble || r == kDouble) return kDouble;
@@ -553,6 +569,9 @@ qsx_operand_t ExpressionFlattener::add(const ScalarPtr &scalar) {
       consts_.push_back(scalar->literal);
       return qsx_operand_t{QSX_OPD_CONST, static_cast<std::int32_t>(consts_.size() - 1)};
     }
+    case Scalar::kCaseExpression:
+      throw ExecutionError("CASE inside an arithmetic expression or inside another CASE's branch: a CASE is the root of a Select "
+                           "scalar or of an aggregate's argument", QSX_ERR_UNSUPPORTED);
     default: {
       const qsx_operand_t a = add(scalar->left), b = add(scalar->right);
       std::int32_t op = static_cast<std::int32_t>(scalar->operation);   // kAdd .. kDivide = QSX_EX_ADD .. QSX_EX_DIV
@@ -575,6 +594,107 @@ qsx_operand_t ExpressionFlattener::add(const ScalarPtr &scalar) {
     }
   }
 }
+
+// ---------------------------------------------------------------------------
+// searched CASE (ScalarCaseExpression::getAllValues, expressions/scalar/ScalarCaseExpression.cpp:273-350)
+// ---------------------------------------------------------------------------
+CaseEvaluator::CaseEvaluator(const ScalarPtr &s, const CatalogRelation &relation, bool integer_arithmetic) : scalar(s) {
+  if (s == nullptr || s->kind != Scalar::kCaseExpression) throw ExecutionError("CaseEvaluator: not a CASE", QSX_ERR_INVALID_ARGUMENT);
+  if (s->whens.empty() || s->whens.size() > QSX_MAX_CASE_WHENS) {
+    throw ExecutionError("CASE: 1 .. QSX_MAX_CASE_WHENS WHEN clauses", QSX_ERR_UNSUPPORTED);
+  }
+  std::memset(&desc, 0, sizeof(desc));
+  ExpressionFlattener flattener([&](attribute_id a) {
+    for (std::size_t c = 0; c < attrs.size(); ++c) if (attrs[c] == a) return static_cast<int>(c);
+    attrs.push_back(a);
+    return static_cast<int>(attrs.size() - 1);
+  }, integer_arithmetic ? &relation : nullptr);
+  const TypeID unified = ScalarResultType(s, relation);   // (throws QSX_ERR_UNSUPPORTED on a CHAR / DATE branch)
+  out_type = integer_arithmetic ? unified : kDouble;
+  desc.num_whens = static_cast<std::int32_t>(s->whens.size());
+  desc.out_type = out_type;
+  const auto branch = [&](const ScalarPtr &value) {
+    if (value == nullptr) {
+      has_null_branch = true;
+      return qsx_operand_t{QSX_OPD_NULL, 0};
+    }
+    if (value->kind == Scalar::kCaseExpression) throw ExecutionError("CASE nested in a branch of a CASE", QSX_ERR_UNSUPPORTED);
+    return flattener.add(value);
+  };
+  for (std::size_t k = 0; k < s->whens.size(); ++k) {
+    for (const ComparisonPredicate &term : s->whens[k].first.conjuncts) {
+      if (IsLikeComparison(term.comparison)) CheckLikeTerm(term, relation.getAttributeType(term.attribute));
+    }
+    desc.value[k] = branch(s->whens[k].second);
+  }
+  desc.value[s->whens.size()] = branch(s->else_result);
+  if (attrs.size() > QSX_MAX_COLUMNS) throw ExecutionError("CASE over too many attributes", QSX_ERR_UNSUPPORTED);
+  instrs = flattener.instrs();
+  for (std::size_t c = 0; c < flattener.consts().size(); ++c) consts[c] = flattener.consts()[c];
+  nullable = has_null_branch;
+  for (attribute_id a : attrs) {
+    types.push_back(relation.getAttributeType(a).id);
+    nullable = nullable || relation.getAttributeType(a).nullable;
+  }
+}
+
+void CaseEvaluator::evalBlock(const StorageBlock &block, void *out_dev, std::uint64_t *out_nulls_dev) const {
+  const std::int64_t n = block.numTuples();
+  if (n == 0) return;
+  struct Owned {
+    std::vector<void *> ptrs;
+    ~Owned() { for (void *p : ptrs) qsx_device_free(p); }
+  } when_bitmaps;
+  const std::uint64_t *whens[QSX_MAX_CASE_WHENS] = {};
+  for (std::size_t k = 0; k < scalar->whens.size(); ++k) {
+    std::int64_t matches = 0;   // the predicate over the WHOLE block: the kernel gives the first match the row
+    when_bitmaps.ptrs.push_back(scalar->whens[k].first.getMatchesForBlock(block, &matches, nullptr));
+    whens[k] = static_cast<const std::uint64_t *>(when_bitmaps.ptrs.back());
+  }
+  const void *cols[QSX_MAX_COLUMNS] = {};
+  const std::uint64_t *col_nulls[QSX_MAX_COLUMNS] = {};
+  for (std::size_t c = 0; c < attrs.size(); ++c) {
+    cols[c] = block.stripe(attrs[c]);
+    col_nulls[c] = block.nullBitmap(attrs[c]);
+  }
+  if (nullable && out_nulls_dev == nullptr) throw ExecutionError("CASE that can yield NULL needs a null bitmap", QSX_ERR_INVALID_ARGUMENT);
+  CheckStatus(qsx_eval_case(static_cast<int>(attrs.size()), cols, types.data(), nullable ? col_nulls : nullptr, static_cast<int>(instrs.size()),
+                            instrs.data(), consts, &desc, whens, n, out_dev, nullable ? out_nulls_dev : nullptr, CurrentStream()),
+              "qsx_eval_case");
+  CheckStatus(qsx_stream_synchronize(CurrentStream()), "qsx_stream_synchronize");   // (the WHEN bitmaps go back)
+}
+
+bool CaseEvaluator::evalBlocks(const std::vector<BlockReference> &blocks, const std::vector<std::int64_t> &rows, void *const *outs,
+                               std::vector<std::unique_ptr<RunMatches>> *keep) const {
+  if (nullable || blocks.empty()) return false;
+  for (const auto &when : scalar->whens) {
+    if (when.first.conjuncts.empty() || !RunPredicateCovers(when.first, blocks)) return false;
+  }
+  for (const BlockReference &b : blocks) {
+    for (attribute_id a : attrs) if (b->nullBitmap(a) != nullptr) return false;
+  }
+  const std::size_t nb = blocks.size(), nw = scalar->whens.size();
+  std::vector<const std::uint64_t *> when_bitmaps(nb * nw);
+  for (std::size_t k = 0; k < nw; ++k) {
+    keep->emplace_back(new RunMatches);
+    RunPredicateMatches(scalar->whens[k].first, blocks, rows, nullptr, keep->back().get());
+    for (std::size_t b = 0; b < nb; ++b) when_bitmaps[b * nw + k] = keep->back()->bitmaps[b];
+  }
+  std::vector<const void *> cols(nb * attrs.size());
+  for (std::size_t b = 0; b < nb; ++b) {
+    for (std::size_t c = 0; c < attrs.size(); ++c) cols[b * attrs.size() + c] = blocks[b]->stripe(attrs[c]);
+  }
+  CheckStatus(qsx_eval_case_blocks(static_cast<int>(attrs.size()), types.data(), static_cast<int>(instrs.size()), instrs.data(), consts, &desc,
+                                   static_cast<std::int64_t>(nb), rows.data(), cols.data(), nullptr, when_bitmaps.data(), outs, nullptr,
+                                   CurrentStream()), "qsx_eval_case_blocks");
+  return true;
+}
+
+struct AggregationOperationState::CaseColumn {
+  int column;
+  CaseEvaluator evaluator;
+  CaseColumn(int c, const ScalarPtr &s, const CatalogRelation &rel, bool integer) : column(c), evaluator(s, rel, integer) {}
+};
 
 AggregationOperationState::AggregationOperationState(const AggregationStateSpec &spec) : spec_(spec) {
   // the library must have been built from the header this file was compiled against
@@ -624,6 +744,24 @@ AggregationOperationState::AggregationOperationState(const AggregationStateSpec 
     const AggregateSpec &ag = spec_.aggregates[a];
     if (ag.is_distinct && !interned_.empty()) {   // (finalizeWithDistinct lines its result sets up by sorting on key VALUES)
       throw ExecutionError("DISTINCT aggregate beside a CHAR(n) group-by key that is interned into ids", QSX_ERR_UNSUPPORTED);
+    }
+    if (ag.argument_expression != nullptr && ag.argument_expression->kind == Scalar::kCaseExpression) {
+      // a CASE argument: a derived column of the state (quickstep_gpu.hpp case_columns_)
+      if (ag.is_distinct) throw ExecutionError("DISTINCT aggregate over a CASE", QSX_ERR_UNSUPPORTED);
+      if (column_attr_.size() >= QSX_MAX_COLUMNS) throw ExecutionError("AggregationOperationState: too many columns", QSX_ERR_UNSUPPORTED);
+      const int column = static_cast<int>(column_attr_.size());
+      case_columns_.emplace_back(new CaseColumn(column, ag.argument_expression, rel, spec.integer_argument_arithmetic));
+      const CaseEvaluator &ev = case_columns_.back()->evaluator;
+      config_.column_type[column] = ev.out_type;
+      config_.column_width[column] = ev.width();
+      config_.column_nullable[column] = ev.nullable ? 1 : 0;
+      column_attr_.push_back(kInvalidAttributeID);
+      // COUNT(CASE ..) counts the rows whose value is not NULL; over a CASE that cannot be NULL it is COUNT(*)
+      config_.aggs[num_main].fn = ag.function == AggregationID::kCount ? (ev.nullable ? QSX_AGG_COUNT : QSX_AGG_COUNT_STAR) : AggFn(ag.function);
+      config_.aggs[num_main].arg.kind = QSX_OPD_COLUMN;
+      config_.aggs[num_main].arg.index = column;
+      main_agg_.push_back(num_main++);
+      continue;
     }
     if (ag.argument_expression != nullptr && ag.is_distinct) {
       // DISTINCT over an arithmetic expression (Distinct.test:58-72 COUNT(DISTINCT x % y) is such a query): the distinctify
@@ -898,12 +1036,31 @@ void AggregationOperationState::aggregateBlock(const StorageBlock &block, const 
   const std::uint64_t *nulls[QSX_MAX_COLUMNS] = {};
   bool any_nulls = false;
   for (std::size_t i = 0; i < column_attr_.size(); ++i) {
+    if (column_attr_[i] == kInvalidAttributeID) continue;   // a derived column: below
     nulls[i] = config_.column_nullable[i] != 0 ? block.nullBitmap(column_attr_[i]) : nullptr;
     any_nulls = any_nulls || nulls[i] != nullptr;
   }
+  // the CASE arguments of the block: their values (and null bitmaps) stand where an attribute's would; they live until the
+  // wait behind the update
+  std::vector<std::unique_ptr<DeviceBuffer>> case_scratch;
+  const void *derived[QSX_MAX_COLUMNS] = {};
+  for (const auto &cc : case_columns_) {
+    case_scratch.emplace_back(new DeviceBuffer(static_cast<std::size_t>(n) * 8 + 16));
+    derived[cc->column] = case_scratch.back()->ptr;
+    std::uint64_t *bits = nullptr;
+    if (cc->evaluator.nullable) {
+      case_scratch.emplace_back(new DeviceBuffer(static_cast<std::size_t>((n + 63) / 64) * 8 + 16));
+      bits = static_cast<std::uint64_t *>(case_scratch.back()->ptr);
+      if (n > 0) {
+        nulls[cc->column] = bits;
+        any_nulls = true;
+      }
+    }
+    cc->evaluator.evalBlock(block, const_cast<void *>(derived[cc->column]), bits);
+  }
   int code_width[QSX_MAX_COLUMNS] = {};
   bool any_coded = false;
-  for (std::size_t i = 0; i < column_attr_.size() && !any_nulls; ++i) {
+  for (std::size_t i = 0; i < column_attr_.size() && !any_nulls && case_columns_.empty(); ++i) {
     const CompressedAttribute *ca = block.compressedAttribute(column_attr_[i]);
     const int type = config_.column_type[i];
     if (ca != nullptr && type != kChar && internedKeyOf(i) < 0 && !block.valuesMaterialized(column_attr_[i])) {
@@ -916,6 +1073,7 @@ void AggregationOperationState::aggregateBlock(const StorageBlock &block, const 
   std::vector<InternRequest> intern(1, InternRequest{&block, lip_filter, {}});
   if (n > 0) internBlocks(&intern, &intern_scratch);
   const auto stripe_of = [&](std::size_t i) -> const void * {
+    if (column_attr_[i] == kInvalidAttributeID) return derived[i];
     const int key = internedKeyOf(i);
     return key >= 0 && n > 0 ? intern[0].ids[key] : block.stripe(column_attr_[i]);
   };
@@ -980,8 +1138,74 @@ void AggregationOperationState::externalizeCodedPredicate() {
   }
 }
 
+// A run of blocks through a state with CASE arguments: the WHEN predicates over the run (RunPredicateMatches), the derived
+// columns by one qsx_eval_case_blocks each, one qsx_agg_update_blocks — when no derived column can be NULL (the TPC-H shape:
+// ELSE 0 over non-nullable attributes) and the run forms cover the blocks; otherwise block by block, like nullable attributes.
+void AggregationOperationState::aggregateBlocksWithCase(const std::vector<BlockReference> &blocks,
+                                                        const std::vector<const std::uint64_t *> &lip_filters) {
+  bool in_run = state_ != nullptr && distinctify_.empty() && external_predicate_.conjuncts.empty();
+  for (const auto &cc : case_columns_) in_run = in_run && !cc->evaluator.nullable;
+  std::vector<BlockReference> run;
+  std::vector<std::int64_t> rows;
+  std::vector<const std::uint64_t *> filters;
+  bool any_filter = false;
+  for (std::size_t i = 0; i < blocks.size() && in_run; ++i) {
+    if (blocks[i]->numTuples() == 0) continue;
+    for (attribute_id a : column_attr_) {
+      if (a != kInvalidAttributeID && blocks[i]->nullBitmap(a) != nullptr) in_run = false;
+    }
+    run.push_back(blocks[i]);
+    rows.push_back(blocks[i]->numTuples());
+    filters.push_back(i < lip_filters.size() ? lip_filters[i] : nullptr);
+    any_filter = any_filter || filters.back() != nullptr;
+  }
+  std::vector<std::unique_ptr<DeviceBuffer>> case_scratch;
+  std::vector<std::unique_ptr<RunMatches>> keep;
+  std::vector<std::vector<void *>> derived(case_columns_.size());
+  for (std::size_t k = 0; k < case_columns_.size() && in_run && !run.empty(); ++k) {
+    for (std::int64_t n : rows) {
+      case_scratch.emplace_back(new DeviceBuffer(static_cast<std::size_t>(n) * 8 + 16));
+      derived[k].push_back(case_scratch.back()->ptr);
+    }
+    in_run = case_columns_[k]->evaluator.evalBlocks(run, rows, derived[k].data(), &keep);
+  }
+  if (!in_run) {
+    CheckStatus(qsx_stream_synchronize(CurrentStream()), "qsx_stream_synchronize");   // (derived columns already queued are dropped)
+    for (std::size_t i = 0; i < blocks.size(); ++i) aggregateBlock(*blocks[i], i < lip_filters.size() ? lip_filters[i] : nullptr);
+    return;
+  }
+  if (run.empty()) return;
+  InternScratch intern_scratch;
+  std::vector<InternRequest> intern;
+  if (!interned_.empty()) {
+    for (std::size_t b = 0; b < run.size(); ++b) intern.push_back(InternRequest{run[b].get(), filters[b], {}});
+    internBlocks(&intern, &intern_scratch);
+  }
+  std::vector<const void *> cols;
+  for (std::size_t b = 0; b < run.size(); ++b) {
+    for (std::size_t c = 0; c < column_attr_.size(); ++c) {
+      const int key = internedKeyOf(c);
+      if (column_attr_[c] == kInvalidAttributeID) {
+        for (std::size_t k = 0; k < case_columns_.size(); ++k) if (static_cast<std::size_t>(case_columns_[k]->column) == c) cols.push_back(derived[k][b]);
+      } else if (key >= 0) {
+        cols.push_back(intern[b].ids[static_cast<std::size_t>(key)]);
+      } else {
+        cols.push_back(run[b]->stripe(column_attr_[c]));
+      }
+    }
+  }
+  CheckStatus(qsx_agg_update_blocks(state_, static_cast<int>(rows.size()), rows.data(), cols.data(), any_filter ? filters.data() : nullptr,
+                                    CurrentStream()), "qsx_agg_update_blocks");
+  case_run_blocks_ += static_cast<std::int64_t>(rows.size());
+  CheckStatus(qsx_stream_synchronize(CurrentStream()), "qsx_stream_synchronize");   // the scratch behind the derived columns and bitmaps goes back
+}
+
 void AggregationOperationState::aggregateBlocks(const std::vector<BlockReference> &blocks,
                                                 const std::vector<const std::uint64_t *> &lip_filters) {
+  if (!case_columns_.empty()) {
+    aggregateBlocksWithCase(blocks, lip_filters);
+    return;
+  }
   std::vector<std::int64_t> rows;
   std::vector<const void *> cols;
   std::vector<const std::uint64_t *> filters;

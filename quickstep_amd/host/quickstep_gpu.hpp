@@ -425,13 +425,26 @@ class Scalar;
 typedef std::shared_ptr<const Scalar> ScalarPtr;
 class Scalar {
  public:
-  enum Kind { kAttribute, kLiteral, kBinaryExpression };
+  enum Kind { kAttribute, kLiteral, kBinaryExpression, kCaseExpression };
   Kind kind = kAttribute;
   attribute_id attribute = kInvalidAttributeID;
   double literal = 0.0;
   TypeID literal_type = kDouble;   // kInt / kLong: an integer literal (ScalarLiteral of an INT / LONG TypedValue)
   BinaryOperationID operation = BinaryOperationID::kAdd;
   ScalarPtr left, right;
+  // kCaseExpression — CASE WHEN p0 THEN e0 WHEN p1 THEN e1 .. ELSE e END (expressions/scalar/ScalarCaseExpression.cpp): the
+  // first WHEN whose predicate holds gives the value; a null else_result is the NULL literal, as the resolver supplies it for
+  // an absent ELSE.  A WHEN is a Predicate, a conjunction: a disjunction of exclusive terms is written as several WHENs with
+  // the same result.  A CASE is the root of a Select scalar or of an aggregate's argument and nowhere else (inside an
+  // arithmetic node or another CASE's branch: QSX_ERR_UNSUPPORTED); its branches are numeric (a CHAR attribute:
+  // QSX_ERR_UNSUPPORTED); predicates and join projections hold attributes and literals only, so no CASE reaches them.
+  std::vector<std::pair<Predicate, ScalarPtr>> whens;
+  ScalarPtr else_result;
+  static ScalarPtr Case(std::vector<std::pair<Predicate, ScalarPtr>> when_then, ScalarPtr else_value) {
+    auto s = std::make_shared<Scalar>();
+    s->kind = kCaseExpression; s->whens = std::move(when_then); s->else_result = std::move(else_value);
+    return s;
+  }
   static ScalarPtr Attribute(attribute_id a) { auto s = std::make_shared<Scalar>(); s->kind = kAttribute; s->attribute = a; return s; }
   static ScalarPtr Literal(double v) { auto s = std::make_shared<Scalar>(); s->kind = kLiteral; s->literal = v; return s; }
   // an INT literal when the value fits 32 bits, else LONG (|v| < 2^53: it travels as a double inside the program)
@@ -454,6 +467,7 @@ class Scalar {
 // (qsx_eval_expression_long) and, when AggregationStateSpec::integer_argument_arithmetic is set, inside the aggregation kernel
 // (QSX_EX_IADD .. IDIV); without that flag aggregate arguments are evaluated in double (exact below 2^53) and typed DOUBLE.
 TypeID ScalarResultType(const ScalarPtr &scalar, const CatalogRelation &relation);
+// A CASE has the unifying type of its branches (the resolver's Cast, Resolver.cpp:2819-2829).
 // Scalar trees flattened into one expression program (qsx_expr_instr_t[]): one instruction per distinct binary node —
 // a subexpression shared by several scalars is computed once, the role of the reference's ColumnVectorCache — input
 // attributes mapped to program columns through `column_of`.
@@ -530,6 +544,8 @@ class AggregationOperationState {
   const AggregationStateSpec &spec() const { return spec_; }
   // blocks aggregated on their code stripes (qsx_agg_update_coded) rather than on decoded values
   std::int64_t numBlocksAggregatedOnCodes() const { return coded_blocks_.load(); }
+  // blocks whose CASE arguments were evaluated by the run form (qsx_eval_case_blocks) and aggregated by one launch over the run
+  std::int64_t numBlocksWithCaseEvaluatedInRuns() const { return case_run_blocks_.load(); }
 
  private:
   AggregationStateSpec spec_;
@@ -545,7 +561,16 @@ class AggregationOperationState {
   bool coded_merged_ = false;
   std::mutex coded_mutex_;
   std::atomic<std::int64_t> coded_blocks_{0};
-  std::vector<attribute_id> column_attr_;  // config column -> input attribute
+  std::vector<attribute_id> column_attr_;  // config column -> input attribute (kInvalidAttributeID: a derived column)
+  // An aggregate whose argument is a CASE reads a DERIVED column of the state: of the CASE's type, nullable exactly when the
+  // CASE has a NULL branch or a nullable operand attribute, computed per block (or per run) in front of the update
+  // (qsx_eval_case / qsx_eval_case_blocks) and handed in where an attribute's stripe would be.  Such a state does not take
+  // the code-stripe state: compressed operand attributes reach the kernels decoded (stripe()), WHEN predicates on coded
+  // attributes keep their coded select paths.
+  struct CaseColumn;
+  std::vector<std::shared_ptr<CaseColumn>> case_columns_;
+  std::atomic<std::int64_t> case_run_blocks_{0};
+  void aggregateBlocksWithCase(const std::vector<BlockReference> &blocks, const std::vector<const std::uint64_t *> &lip_filters);
   // conjuncts the state's kernel does not evaluate itself (CHAR(n) comparisons, terms beyond QSX_MAX_PRED_TERMS): they are
   // evaluated per block like a SelectOperator's predicate and handed to the update as its filter
   Predicate external_predicate_;

@@ -136,8 +136,9 @@ std::uint64_t NowMicros();
 // NULL handling shared by the aggregation state and the operators (storage.cpp)
 std::unique_ptr<DeviceBuffer> NotNullFilter(const StorageBlock &block, const std::vector<attribute_id> &attrs, const std::uint64_t *filter);
 void GatherBlockNulls(const StorageBlock &block, attribute_id attr, const void *tids, std::int64_t n, std::uint64_t *dst);
+// derived: nullptr, or per output attribute a null bitmap over the block's tuples that is not an attribute's (a CASE's) or nullptr
 void ProjectNullBitmaps(const StorageBlock &block, const std::vector<attribute_id> &selection, const void *bitmap,
-                        std::int64_t num_selected, StorageBlock *out);
+                        std::int64_t num_selected, StorageBlock *out, const std::vector<const std::uint64_t *> *derived = nullptr);
 
 // ---- the join key of a block / of a run of blocks as the join table sees it (BuildHash and HashJoin work orders) ----
 // The single key column the join table sees for one block: the attribute's stripe, or — for a
@@ -293,6 +294,32 @@ void SelectCharTerm(const ComparisonPredicate &term, const void *stripe, int wid
 bool RunPredicateCovers(const Predicate &predicate, const std::vector<BlockReference> &blocks);
 void RunPredicateMatches(const Predicate &predicate, const std::vector<BlockReference> &blocks, const std::vector<std::int64_t> &rows,
                          const std::uint64_t *const *in_filters, RunMatches *out);
+
+
+// A Scalar::kCaseExpression ready to be evaluated (query_context.cpp): the branch values flattened into ONE program — integer
+// subtrees as integer instructions when integer_arithmetic, a subexpression two branches share once — and the qsx_case_desc_t
+// over it.  QSX_ERR_UNSUPPORTED: no or more than QSX_MAX_CASE_WHENS WHENs, a CASE nested in a branch, a CHAR-typed branch.
+struct CaseEvaluator {
+  CaseEvaluator(const ScalarPtr &scalar, const CatalogRelation &relation, bool integer_arithmetic);
+  ScalarPtr scalar;
+  std::vector<attribute_id> attrs;                 // program column -> attribute
+  std::vector<std::int32_t> types;
+  std::vector<qsx_expr_instr_t> instrs;
+  double consts[QSX_MAX_CONSTS] = {};
+  qsx_case_desc_t desc;
+  TypeID out_type = kDouble;
+  bool has_null_branch = false;
+  bool nullable = false;                           // a NULL branch, or a nullable operand attribute: the value can be NULL
+  int width() const { return out_type == kInt ? 4 : 8; }
+  // The CASE over the whole block: n values into out_dev and, when `nullable`, the null bitmap into out_nulls_dev.  The WHEN
+  // bitmaps live until the call's wait: this synchronises.
+  void evalBlock(const StorageBlock &block, void *out_dev, std::uint64_t *out_nulls_dev) const;
+  // The same over a run in one launch per WHEN term and one qsx_eval_case_blocks; false (nothing done) when the run forms do
+  // not cover it: a value that can be NULL, a WHEN RunPredicateCovers refuses, a block with a null bitmap on an operand.
+  // The bitmaps stay in `keep` until the caller has waited for the stream.
+  bool evalBlocks(const std::vector<BlockReference> &blocks, const std::vector<std::int64_t> &rows, void *const *outs,
+                  std::vector<std::unique_ptr<RunMatches>> *keep) const;
+};
 
 }  // namespace quickstep
 

@@ -241,7 +241,9 @@ void SelectWorkOrder::executeBlock(block_id input_block_id) {
   std::vector<std::int32_t> widths;
   std::vector<std::unique_ptr<DeviceBuffer>> expression_values;
   std::vector<attribute_id> null_sources;   // per output attribute: the input attribute whose null bitmap it inherits
+  std::vector<const std::uint64_t *> derived_nulls;   // ... or a null bitmap of its own (a CASE's), over the block's tuples
   if (selection_ != nullptr && !selection_->empty()) {
+    derived_nulls.assign(selection_->size(), nullptr);
     for (std::size_t i = 0; i < selection_->size(); ++i) {
       const ScalarPtr &scalar = (*selection_)[i];
       dst.push_back(out->stripe(static_cast<attribute_id>(i)));
@@ -249,6 +251,29 @@ void SelectWorkOrder::executeBlock(block_id input_block_id) {
         src.push_back(block->stripe(scalar->attribute));
         widths.push_back(block->getRelation().getAttributeType(scalar->attribute).width);
         null_sources.push_back(scalar->attribute);
+        continue;
+      }
+      if (scalar->kind == Scalar::kCaseExpression) {
+        // ScalarCaseExpression: every WHEN over the whole block, one multiplexing pass (qsx_eval_case), then the matching rows
+        // like any expression value; its null bitmap follows the output tuples like an attribute's
+        const CaseEvaluator evaluator(scalar, block->getRelation(), true);
+        const Type &out_type = out->getRelation().getAttributeType(static_cast<attribute_id>(i));
+        if (out_type.width != evaluator.width() || (evaluator.nullable && !out_type.nullable)) {
+          throw ExecutionError("SelectWorkOrder: the output attribute of a CASE must have the unifying type of its branches and be "
+                               "nullable when the CASE can yield NULL", QSX_ERR_INVALID_ARGUMENT);
+        }
+        expression_values.emplace_back(new DeviceBuffer(static_cast<std::size_t>(n > 0 ? n : 1) * 8));
+        void *values = expression_values.back()->ptr;
+        std::uint64_t *bits = nullptr;
+        if (evaluator.nullable) {
+          expression_values.emplace_back(new DeviceBuffer(static_cast<std::size_t>((n + 63) / 64) * 8 + 16));
+          bits = static_cast<std::uint64_t *>(expression_values.back()->ptr);
+          if (n > 0) derived_nulls[i] = bits;
+        }
+        evaluator.evalBlock(*block, values, bits);
+        src.push_back(values);
+        widths.push_back(evaluator.width());
+        null_sources.push_back(kInvalidAttributeID);
         continue;
       }
       // ScalarBinaryExpression / ScalarLiteral: one fused pass over the operand stripes (qsx_eval_expression)
@@ -306,7 +331,7 @@ void SelectWorkOrder::executeBlock(block_id input_block_id) {
                                  static_cast<std::int64_t *>(count.ptr), ws.ptr, ws_bytes, CurrentStream()),
               "qsx_compact_gather");
   const std::int64_t written = ReadCount(count.ptr);  // synchronises the work order, like the reference's execute()
-  ProjectNullBitmaps(*block, null_sources, bitmap, written, out.get());
+  ProjectNullBitmaps(*block, null_sources, bitmap, written, out.get(), &derived_nulls);
   qsx_device_free(bitmap);
   output_destination_->returnBlock(out_id, written, getPartitionId());
 }

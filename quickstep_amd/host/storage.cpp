@@ -949,12 +949,15 @@ void GatherBlockNulls(const StorageBlock &block, attribute_id attr, const void *
 // bits of input attribute selection[i] at the tuples set in `bitmap` (bulkInsertTuplesWithRemappedAttributes copies
 // value and null bit together, storage/BasicColumnStoreTupleStorageSubBlock.cpp:339-425).
 void ProjectNullBitmaps(const StorageBlock &block, const std::vector<attribute_id> &selection, const void *bitmap,
-                        std::int64_t num_selected, StorageBlock *out) {
+                        std::int64_t num_selected, StorageBlock *out, const std::vector<const std::uint64_t *> *derived) {
   const std::int64_t n = block.numTuples();
   std::unique_ptr<DeviceBuffer> tids;
   for (std::size_t i = 0; i < selection.size(); ++i) {
-    if (selection[i] == kInvalidAttributeID) continue;          // an expression's value: no bitmap to carry over
-    if (block.nullBitmap(selection[i]) == nullptr) continue;   // the output bitmap stays all-zero
+    const std::uint64_t *own = derived != nullptr && i < derived->size() ? (*derived)[i] : nullptr;   // a CASE's null bitmap
+    if (own == nullptr) {
+      if (selection[i] == kInvalidAttributeID) continue;          // an expression's value: no bitmap to carry over
+      if (block.nullBitmap(selection[i]) == nullptr) continue;   // the output bitmap stays all-zero
+    }
     std::uint64_t *dst = out->nullBitmap(static_cast<attribute_id>(i));
     if (dst == nullptr) throw ExecutionError("projection of a nullable attribute into a non-nullable one", QSX_ERR_INVALID_ARGUMENT);
     if (num_selected == 0) continue;
@@ -966,7 +969,13 @@ void ProjectNullBitmaps(const StorageBlock &block, const std::vector<attribute_i
                                      static_cast<std::int64_t *>(count.ptr), ws.ptr, ws_bytes, CurrentStream()), "qsx_bitmap_to_tids");
       CheckStatus(qsx_stream_synchronize(CurrentStream()), "qsx_stream_synchronize");   // ws / count are locals
     }
-    GatherBlockNulls(block, selection[i], tids->ptr, num_selected, dst);
+    if (own != nullptr) {
+      const std::int64_t zero = 0;
+      CheckStatus(qsx_bitmap_gather_segmented(1, &own, &zero, static_cast<const std::int32_t *>(tids->ptr), num_selected, dst, CurrentStream()),
+                  "qsx_bitmap_gather_segmented");
+    } else {
+      GatherBlockNulls(block, selection[i], tids->ptr, num_selected, dst);
+    }
   }
   if (tids != nullptr) CheckStatus(qsx_stream_synchronize(CurrentStream()), "qsx_stream_synchronize");
 }

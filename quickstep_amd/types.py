@@ -21,6 +21,7 @@ AGG_SINGLE_STATE, AGG_COMPACT_KEY, AGG_COLLISION_FREE, AGG_GENERIC = range(4)
 AGG_COUNT_STAR, AGG_SUM, AGG_AVG, AGG_MIN, AGG_MAX, AGG_COUNT = range(6)
 # qsx_operand_kind_t
 OPD_COLUMN, OPD_CONST, OPD_TEMP = range(3)
+OPD_NULL = 3                                                        # QSX_OPD_NULL: the NULL literal, a branch value of qsx_eval_case only
 # qsx_expr_op_t
 EX_ADD, EX_SUB, EX_MUL, EX_DIV = range(4)
 EX_IADD, EX_ISUB, EX_IMUL, EX_IDIV = range(4, 8)                    # the same in integer arithmetic (include/qsx.h)
@@ -28,6 +29,7 @@ EX_IADD, EX_ISUB, EX_IMUL, EX_IDIV = range(4, 8)                    # the same i
 LIP_SINGLE_IDENTITY_HASH, LIP_BITVECTOR_EXACT = range(2)
 
 MAX_COLUMNS, MAX_KEYS, MAX_AGGS, MAX_INSTRS, MAX_TEMPS, MAX_CONSTS, MAX_PRED_TERMS = 16, 4, 8, 16, 8, 8, 4
+MAX_CASE_WHENS = 8                                                  # QSX_MAX_CASE_WHENS
 
 TYPE_WIDTH = {INT: 4, LONG: 8, FLOAT: 4, DOUBLE: 8, DATE: 8}
 
@@ -54,6 +56,10 @@ class ExprInstr(C.Structure):
 
 class AggDesc(C.Structure):
     _fields_ = [("fn", C.c_int32), ("arg", Operand)]
+
+
+class CaseDesc(C.Structure):                                         # qsx_case_desc_t
+    _fields_ = [("num_whens", C.c_int32), ("value", Operand * (MAX_CASE_WHENS + 1)), ("out_type", C.c_int32)]
 
 
 class PredLiteral(C.Union):
@@ -96,6 +102,20 @@ def const(i):
 
 def temp(i):
     return Operand(OPD_TEMP, i)
+
+
+def null():
+    return Operand(OPD_NULL, 0)
+
+
+def make_case_desc(values, out_type):
+    """qsx_case_desc_t: values = the THEN operand of every WHEN, then the ELSE operand (T.null(): NULL)."""
+    d = CaseDesc()
+    d.num_whens = len(values) - 1
+    for k, v in enumerate(values[:MAX_CASE_WHENS + 1]):
+        d.value[k] = v
+    d.out_type = out_type
+    return d
 
 
 def make_agg_config(strategy, columns, keys=(), instrs=(), consts=(), aggs=(), pred=(),

@@ -867,6 +867,44 @@ int qsx_eval_case_blocks(int num_columns, const int32_t *types, int num_instrs, 
                          const uint64_t *const *block_when_bitmaps, void *const *block_out,
                          uint64_t *const *block_out_null_bitmaps, qsx_stream_t stream);
 
+/* Unary operations (types/operations/unary_operations/): EXTRACT(YEAR | MONTH FROM date) and SUBSTRING.  TPC-H Q7, Q8 and Q9
+ * project extract(year from ..) and group by it, Q22 does both with substring(c_phone from 1 for 2).  QSX_ABI_VERSION did not
+ * change: a caller detects the capability by the presence of the symbols.
+ *
+ * qsx_eval_date_extract: out[i] = the year or the month of dates[i] as an INT — what DateExtractUncheckedOperator computes
+ * per value (types/operations/unary_operations/DateExtractOperation.cpp:117-142, 277-286: yearField() / monthField() of a
+ * DateLit, types/DatetimeLit.hpp:38-43; the 8-byte layout of QSX_DATE above).
+ *   unit       QSX_DATE_YEAR: any int32, negative years included; QSX_DATE_MONTH: byte 4 of the value.  On a Date only these
+ *              two exist (DateExtractOperation.cpp:277-286); DAY / HOUR / MINUTE / SECOND belong to Datetime, which this
+ *              library has no type for: any other unit is QSX_ERR_UNSUPPORTED.
+ *   dates_dev  n values of 8 bytes, 8-byte aligned; out_dev: n INTs, 4-byte aligned (else QSX_ERR_INVALID_ARGUMENT).
+ *   NULL       the kernel sees no bitmap: the result is nullable exactly when the argument is, the caller carries the
+ *              argument's null bitmap over, and the output row of a NULL input is unspecified.
+ *
+ * qsx_eval_substring: SubstringUncheckedOperator::computeSubstring (types/operations/unary_operations/
+ * SubstringOperation.cpp:74-91) over a CHAR(width) stripe.  `start` is 0-BASED, as SubstringOperation::Instance takes it
+ * (SQL's FROM 1 is start = 0).
+ *   Result     CHAR(m) with m = min(width - start, length) (SubstringOperation.hpp:174-182): n fields of m bytes in out_dev.
+ *              len = the field's length up to its first NUL or `width` bytes.  start >= len: the empty string.  Otherwise the
+ *              min(len - start, length) bytes from `start` on.  Bytes >= 0x80 are copied as they are.
+ *   Padding    the reference writes one NUL behind a short result and leaves the rest of the field as it was; here the field
+ *              is ZERO-FILLED to m — the canonical form of qsx_char_dict_values, so equal texts are equal bytes.
+ *   Bounds     exactly n * m bytes of out_dev are written, whatever its alignment.
+ *   NULL       as above.
+ * start < 0, start >= width, length < 1, width outside 1..255, n < 0 or NULL pointers with n > 0: QSX_ERR_INVALID_ARGUMENT.
+ *
+ * The _blocks forms work on a run of blocks in one launch (host arrays of device pointers, as qsx_select_like_blocks; a block of
+ * 0 rows may stand anywhere): every block's output is that of the single call on that block, byte for byte.
+ * n == 0 / num_blocks == 0 succeed and launch nothing.  Without a device: QSX_ERR_NO_DEVICE, in front of everything. */
+#define QSX_DATE_YEAR 0
+#define QSX_DATE_MONTH 1
+int qsx_eval_date_extract(int unit, const void *dates_dev, int64_t n, int32_t *out_dev, qsx_stream_t stream);
+int qsx_eval_date_extract_blocks(int unit, int64_t num_blocks, const int64_t *block_rows,
+                                 const void *const *block_cols, int32_t *const *block_out, qsx_stream_t stream);
+int qsx_eval_substring(const void *col_dev, int width, int64_t n, int start, int length, void *out_dev, qsx_stream_t stream);
+int qsx_eval_substring_blocks(int width, int64_t num_blocks, const int64_t *block_rows, const void *const *block_cols,
+                              int start, int length, void *const *block_out, qsx_stream_t stream);
+
 typedef struct qsx_agg_config {
   int32_t strategy;                       /* qsx_agg_strategy_t */
   int32_t num_columns;                    /* columns handed to every qsx_agg_update */

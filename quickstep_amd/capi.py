@@ -132,6 +132,10 @@ _SIGNATURES = {
                              _i64, _vp, _vp, _vp]),
     "qsx_eval_case_blocks": (_int, [_int, C.POINTER(_i32), _int, C.POINTER(T.ExprInstr), C.POINTER(C.c_double), C.POINTER(T.CaseDesc), _i64,
                                     C.POINTER(_i64), _pp, _pp, _pp, _pp, _pp, _vp]),
+    "qsx_eval_date_extract": (_int, [_int, _vp, _i64, _vp, _vp]),
+    "qsx_eval_date_extract_blocks": (_int, [_int, _i64, C.POINTER(_i64), _pp, _pp, _vp]),
+    "qsx_eval_substring": (_int, [_vp, _int, _i64, _int, _int, _vp, _vp]),
+    "qsx_eval_substring_blocks": (_int, [_int, _i64, C.POINTER(_i64), _pp, _int, _int, _pp, _vp]),
     "qsx_agg_state_create": (_int, [C.POINTER(T.AggConfig), _pp]),
     "qsx_agg_state_destroy": (_int, [_vp]),
     "qsx_select_cmp_sorted_blocks": (_int, [_int, _i64, C.POINTER(_i64), _pp, _int, _vp, _pp, _pp, _vp, _vp]),
@@ -402,6 +406,58 @@ def select_like_blocks(cols, pattern, negate=False, filters=None, stream=None):
     _check(_lib.qsx_select_like_blocks(width, nb, rows, cptr, C.c_char_p(pattern), len(pattern), int(negate), fptr, optr, _ptr(counts),
                                        _stream(stream)), "qsx_select_like_blocks")
     return outs, counts[:nb]
+
+
+def eval_date_extract(unit, dates, out=None, stream=None):
+    """EXTRACT(YEAR | MONTH FROM date): dates is an int64 tensor of raw DateLit bytes (T.date_raw), unit T.DATE_YEAR or
+    T.DATE_MONTH; returns an int32 tensor.  NULLs are the caller's: the result inherits the argument's null bitmap."""
+    n = dates.numel()
+    assert dates.dtype == torch.int64
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=dates.device)
+    _check(_lib.qsx_eval_date_extract(int(unit), _ptr(dates), n, _ptr(out), _stream(stream)), "qsx_eval_date_extract")
+    return out
+
+
+def eval_date_extract_blocks(unit, blocks, outs=None, stream=None):
+    """eval_date_extract over a run of blocks in one launch: blocks = one int64 stripe per block; returns the int32 stripes."""
+    nb = len(blocks)
+    if outs is None:
+        outs = [torch.empty(b.numel(), dtype=torch.int32, device=b.device) for b in blocks]
+    rows = (C.c_int64 * max(nb, 1))(*[b.numel() for b in blocks])
+    cptr = (C.c_void_p * max(nb, 1))(*[b.data_ptr() if b.numel() else None for b in blocks])
+    optr = (C.c_void_p * max(nb, 1))(*[o.data_ptr() if b.numel() else None for b, o in zip(blocks, outs)])
+    _check(_lib.qsx_eval_date_extract_blocks(int(unit), nb, rows, cptr, optr, _stream(stream)), "qsx_eval_date_extract_blocks")
+    return outs
+
+
+def substring_width(width, start, length):
+    """The m of the CHAR(m) that SUBSTRING over CHAR(width) yields (SubstringOperation.hpp:174-182)."""
+    return min(width - start, length)
+
+
+def eval_substring(col, start, length, out=None, stream=None):
+    """SUBSTRING over a CHAR(width) stripe: col is a uint8 tensor of shape (n, width), start is 0-based (SQL's FROM 1 is 0).
+    Returns a uint8 tensor of shape (n, m), m = min(width - start, length), every text zero-filled to m."""
+    n, width = col.shape
+    assert col.dtype == torch.uint8
+    if out is None:
+        out = torch.empty((n, max(substring_width(width, start, length), 0)), dtype=torch.uint8, device=col.device)
+    _check(_lib.qsx_eval_substring(_ptr(col), width, n, int(start), int(length), _ptr(out), _stream(stream)), "qsx_eval_substring")
+    return out
+
+
+def eval_substring_blocks(cols, start, length, outs=None, stream=None):
+    """eval_substring over a run of blocks in one launch: cols = uint8 tensors of shape (n_b, width)."""
+    nb = len(cols)
+    width = cols[0].shape[1]
+    if outs is None:
+        outs = [torch.empty((c.shape[0], max(substring_width(width, start, length), 0)), dtype=torch.uint8, device=c.device) for c in cols]
+    rows = (C.c_int64 * max(nb, 1))(*[c.shape[0] for c in cols])
+    cptr = (C.c_void_p * max(nb, 1))(*[c.data_ptr() if c.shape[0] else None for c in cols])
+    optr = (C.c_void_p * max(nb, 1))(*[o.data_ptr() if c.shape[0] else None for c, o in zip(cols, outs)])
+    _check(_lib.qsx_eval_substring_blocks(width, nb, rows, cptr, int(start), int(length), optr, _stream(stream)), "qsx_eval_substring_blocks")
+    return outs
 
 
 def char_dict_hash(text, width):

@@ -548,12 +548,40 @@ TypeID ScalarResultType(const ScalarPtr &scalar, const CatalogRelation &relation
       if (!any) throw ExecutionError("CASE: every branch is NULL", QSX_ERR_UNSUPPORTED);
       return unified;
     }
+    case Scalar::kUnaryExpression:
+      return UnaryResultType(scalar, relation).id;
     default: {
       const TypeID l = ScalarResultType(scalar->left, relation), r = ScalarResultType(scalar->right, relation);
+      if (l == kChar || r == kChar) throw ExecutionError("arithmetic over a SUBSTRING", QSX_ERR_UNSUPPORTED);
       if (l == kDouble || r == kDouble) return kDouble;
       return l == kLong || r == kLong ? kLong : kInt;
     }
   }
+}
+
+// DateExtractOperation::resultTypeForArgumentType (an INT, nullable as the argument) and SubstringOperation.hpp:174-182.
+Type UnaryResultType(const ScalarPtr &scalar, const CatalogRelation &relation) {
+  if (scalar == nullptr || scalar->kind != Scalar::kUnaryExpression) throw ExecutionError("UnaryResultType: not a unary expression", QSX_ERR_INVALID_ARGUMENT);
+  if (scalar->operand == nullptr || scalar->operand->kind != Scalar::kAttribute) {
+    throw ExecutionError("EXTRACT / SUBSTRING: the operand must be an attribute (not a literal, an expression, a CASE or another unary)",
+                         QSX_ERR_UNSUPPORTED);
+  }
+  const Type &t = relation.getAttributeType(scalar->operand->attribute);
+  Type result = Type::Int();
+  if (scalar->unary_operation == UnaryOperationID::kDateExtract) {
+    if (t.id != kDate) throw ExecutionError("EXTRACT: the operand must be a DATE attribute", QSX_ERR_UNSUPPORTED);
+    if (scalar->date_extract_unit != QSX_DATE_YEAR && scalar->date_extract_unit != QSX_DATE_MONTH) {
+      throw ExecutionError("EXTRACT: a Date has a YEAR and a MONTH (DAY / HOUR / MINUTE / SECOND belong to Datetime)", QSX_ERR_UNSUPPORTED);
+    }
+  } else {
+    if (t.id != kChar) throw ExecutionError("SUBSTRING: the operand must be a CHAR(n) attribute", QSX_ERR_UNSUPPORTED);
+    if (scalar->substring_start < 0 || scalar->substring_start >= t.width || scalar->substring_length < 1 || t.width < 1 || t.width > 255) {
+      throw ExecutionError("SUBSTRING: 0 <= start < width, length >= 1, width 1..255", QSX_ERR_INVALID_ARGUMENT);
+    }
+    result = Type::Char(t.width - scalar->substring_start < scalar->substring_length ? t.width - scalar->substring_start : scalar->substring_length);
+  }
+  result.nullable = t.nullable;
+  return result;
 }
 
 qsx_operand_t ExpressionFlattener::add(const ScalarPtr &scalar) {
@@ -572,6 +600,13 @@ qsx_operand_t ExpressionFlattener::add(const ScalarPtr &scalar) {
     case Scalar::kCaseExpression:
       throw ExecutionError("CASE inside an arithmetic expression or inside another CASE's branch: a CASE is the root of a Select "
                            "scalar or of an aggregate's argument", QSX_ERR_UNSUPPORTED);
+    case Scalar::kUnaryExpression:
+      if (scalar->unary_operation != UnaryOperationID::kDateExtract) throw ExecutionError("SUBSTRING inside an arithmetic expression", QSX_ERR_UNSUPPORTED);
+      if (!column_of_unary_) {
+        throw ExecutionError("EXTRACT inside a CASE or an aggregate's argument: a unary expression is a Select scalar (or a leaf of its "
+                             "arithmetic) or a group-by key", QSX_ERR_UNSUPPORTED);
+      }
+      return qsx_operand_t{QSX_OPD_COLUMN, column_of_unary_(scalar)};
     default: {
       const qsx_operand_t a = add(scalar->left), b = add(scalar->right);
       std::int32_t op = static_cast<std::int32_t>(scalar->operation);   // kAdd .. kDivide = QSX_EX_ADD .. QSX_EX_DIV
@@ -690,13 +725,103 @@ bool CaseEvaluator::evalBlocks(const std::vector<BlockReference> &blocks, const 
   return true;
 }
 
+// ---------------------------------------------------------------------------
+// unary operations (types/operations/unary_operations/DateExtractOperation.cpp, SubstringOperation.cpp)
+// ---------------------------------------------------------------------------
+UnaryEvaluator::UnaryEvaluator(const ScalarPtr &s, const CatalogRelation &relation) : scalar(s) {
+  result = UnaryResultType(s, relation);   // (checks the operand and the window)
+  operand = s->operand->attribute;
+  operand_type = relation.getAttributeType(operand);
+}
+
+bool UnaryEvaluator::extractsOnCodes(const StorageBlock &block) const {
+  if (scalar->unary_operation != UnaryOperationID::kDateExtract) return false;
+  const CompressedAttribute *ca = block.compressedAttribute(operand);
+  return ca != nullptr && ca->kind == CompressedAttribute::kDictionary && !block.valuesMaterialized(operand) && ca->num_codes > 0 &&
+         (reinterpret_cast<std::uintptr_t>(ca->dictionary) & 7) == 0;   // (a dictionary inside an adopted image may lie anywhere)
+}
+
+bool UnaryEvaluator::evalBlock(const StorageBlock &block, void *out_dev, Scratch *keep) const {
+  const std::int64_t n = block.numTuples();
+  if (n == 0) return false;
+  if (scalar->unary_operation == UnaryOperationID::kSubstring) {
+    CheckStatus(qsx_eval_substring(block.stripe(operand), operand_type.width, n, scalar->substring_start, scalar->substring_length, out_dev,
+                                   CurrentStream()), "qsx_eval_substring");
+    return false;
+  }
+  if (!extractsOnCodes(block)) {
+    CheckStatus(qsx_eval_date_extract(scalar->date_extract_unit, block.stripe(operand), n, static_cast<std::int32_t *>(out_dev), CurrentStream()),
+                "qsx_eval_date_extract");
+    return false;
+  }
+  const CompressedAttribute *ca = block.compressedAttribute(operand);
+  const std::size_t codes = static_cast<std::size_t>(ca->num_codes);
+  keep->emplace_back(new DeviceBuffer((codes + 1) * 4 + 16));
+  std::int32_t *fields = static_cast<std::int32_t *>(keep->back()->ptr);
+  CheckStatus(qsx_eval_date_extract(scalar->date_extract_unit, ca->dictionary, ca->num_codes, fields, CurrentStream()), "qsx_eval_date_extract(dictionary)");
+  CheckStatus(qsx_memset_device(fields + codes, 0, 4, CurrentStream()), "qsx_memset_device");   // the NULL code's entry
+  CheckStatus(qsx_decode_codes(ca->code_width, ca->codes, n, fields, 4, out_dev, CurrentStream()), "qsx_decode_codes(extract)");
+  return true;
+}
+
+std::int64_t UnaryEvaluator::evalBlocks(const std::vector<BlockReference> &blocks, const std::vector<std::int64_t> &rows, void *const *outs,
+                                        Scratch *keep) const {
+  std::int64_t on_codes = 0;
+  std::vector<std::int64_t> run_rows;
+  std::vector<const void *> run_cols;
+  std::vector<void *> run_outs;
+  for (std::size_t b = 0; b < blocks.size(); ++b) {
+    if (rows[b] == 0) continue;
+    if (extractsOnCodes(*blocks[b])) {
+      on_codes += evalBlock(*blocks[b], outs[b], keep) ? 1 : 0;
+      continue;
+    }
+    run_rows.push_back(rows[b]);
+    run_cols.push_back(blocks[b]->stripe(operand));
+    run_outs.push_back(outs[b]);
+  }
+  if (run_rows.empty()) return on_codes;
+  if (scalar->unary_operation == UnaryOperationID::kSubstring) {
+    CheckStatus(qsx_eval_substring_blocks(operand_type.width, static_cast<std::int64_t>(run_rows.size()), run_rows.data(), run_cols.data(),
+                                          scalar->substring_start, scalar->substring_length, run_outs.data(), CurrentStream()),
+                "qsx_eval_substring_blocks");
+  } else {
+    CheckStatus(qsx_eval_date_extract_blocks(scalar->date_extract_unit, static_cast<std::int64_t>(run_rows.size()), run_rows.data(), run_cols.data(),
+                                             reinterpret_cast<std::int32_t *const *>(run_outs.data()), CurrentStream()),
+                "qsx_eval_date_extract_blocks");
+  }
+  return on_codes;
+}
+
+struct AggregationOperationState::UnaryColumn {
+  int column;
+  UnaryEvaluator evaluator;
+  UnaryColumn(int c, const ScalarPtr &s, const CatalogRelation &rel) : column(c), evaluator(s, rel) {}
+};
+
 struct AggregationOperationState::CaseColumn {
   int column;
   CaseEvaluator evaluator;
   CaseColumn(int c, const ScalarPtr &s, const CatalogRelation &rel, bool integer) : column(c), evaluator(s, rel, integer) {}
 };
 
-AggregationOperationState::AggregationOperationState(const AggregationStateSpec &spec) : spec_(spec) {
+AggregationOperationState::AggregationOperationState(const AggregationStateSpec &given) : spec_(given) {
+  // group_by_scalars replaces group_by; a list of attributes only is the plain form
+  if (!spec_.group_by_scalars.empty()) {
+    bool attributes_only = true;
+    for (const ScalarPtr &key : spec_.group_by_scalars) {
+      if (key == nullptr || (key->kind != Scalar::kAttribute && key->kind != Scalar::kUnaryExpression)) {
+        throw ExecutionError("AggregationOperationState: a group-by key is an attribute or a unary expression over one", QSX_ERR_UNSUPPORTED);
+      }
+      attributes_only = attributes_only && key->kind == Scalar::kAttribute;
+    }
+    spec_.group_by.clear();
+    if (attributes_only) {
+      for (const ScalarPtr &key : spec_.group_by_scalars) spec_.group_by.push_back(key->attribute);
+      spec_.group_by_scalars.clear();
+    }
+  }
+  const AggregationStateSpec &spec = spec_;
   // the library must have been built from the header this file was compiled against
   if (qsx_abi_version() != QSX_ABI_VERSION || qsx_abi_sizeof_agg_config() != sizeof(qsx_agg_config_t)) {
     throw ExecutionError("libqsx.so and include/qsx.h disagree on the ABI version / qsx_agg_config_t", QSX_ERR_INVALID_ARGUMENT);
@@ -715,18 +840,44 @@ AggregationOperationState::AggregationOperationState(const AggregationStateSpec 
     column_attr_.push_back(attr);
     return static_cast<int>(column_attr_.size() - 1);
   };
-  config_.strategy = spec.group_by.empty() ? QSX_AGG_SINGLE_STATE : spec.strategy;
-  config_.num_keys = static_cast<int>(spec.group_by.size());
-  for (std::size_t k = 0; k < spec.group_by.size(); ++k) config_.key_column[k] = column_of(spec.group_by[k]);
+  // the group-by keys: attributes, or (group_by_scalars) attributes and unary expressions, each of the latter a derived column
+  const std::size_t num_keys = spec.group_by_scalars.empty() ? spec.group_by.size() : spec.group_by_scalars.size();
+  if (num_keys > QSX_MAX_KEYS) throw ExecutionError("AggregationOperationState: too many group-by keys", QSX_ERR_UNSUPPORTED);
+  std::vector<Type> key_types;               // a unary key: its result type
+  std::vector<attribute_id> key_attributes;  // ... and its operand attribute
+  config_.strategy = num_keys == 0 ? QSX_AGG_SINGLE_STATE : spec.strategy;
+  config_.num_keys = static_cast<int>(num_keys);
+  for (std::size_t k = 0; k < num_keys; ++k) {
+    const ScalarPtr unary = !spec.group_by_scalars.empty() && spec.group_by_scalars[k]->kind == Scalar::kUnaryExpression ? spec.group_by_scalars[k] : nullptr;
+    if (unary == nullptr) {
+      const attribute_id attr = spec.group_by_scalars.empty() ? spec.group_by[k] : spec.group_by_scalars[k]->attribute;
+      config_.key_column[k] = column_of(attr);
+      key_types.push_back(rel.getAttributeType(attr));
+      key_attributes.push_back(attr);
+      continue;
+    }
+    if (column_attr_.size() >= QSX_MAX_COLUMNS) throw ExecutionError("AggregationOperationState: too many columns", QSX_ERR_UNSUPPORTED);
+    const int column = static_cast<int>(column_attr_.size());
+    unary_columns_.emplace_back(new UnaryColumn(column, unary, rel));
+    const UnaryEvaluator &ev = unary_columns_.back()->evaluator;
+    config_.column_type[column] = ev.result.id;
+    config_.column_width[column] = ev.result.width;
+    config_.column_nullable[column] = ev.result.nullable ? 1 : 0;
+    column_attr_.push_back(kInvalidAttributeID);
+    config_.key_column[k] = column;
+    key_types.push_back(ev.result);
+    key_attributes.push_back(ev.operand);
+  }
   // GROUP BY CHAR(n): the widths the state packs itself (1, 2, 4, 8 bytes under COMPACT_KEY) keep their path; every other
   // CHAR group-by attribute is presented as an INT column of ids out of a device dictionary of its values
-  for (std::size_t k = 0; k < spec.group_by.size(); ++k) {
-    const Type &t = rel.getAttributeType(spec.group_by[k]);
+  for (std::size_t k = 0; k < num_keys; ++k) {
+    const Type &t = key_types[k];
     const bool packs = t.width == 1 || t.width == 2 || t.width == 4 || t.width == 8;
     if (t.id != kChar || (packs && config_.strategy != QSX_AGG_GENERIC) || internedKeyOf(config_.key_column[k]) >= 0) continue;
     InternedKey key;
     key.column = config_.key_column[k];
-    key.attribute = spec.group_by[k];
+    key.attribute = key_attributes[k];
+    key.derived = column_attr_[static_cast<std::size_t>(key.column)] == kInvalidAttributeID;
     key.width = t.width;
     key.capacity = spec.estimated_num_groups > 16 ? spec.estimated_num_groups : 16;
     if (key.capacity > (std::int64_t(1) << 30)) key.capacity = std::int64_t(1) << 30;
@@ -742,6 +893,12 @@ AggregationOperationState::AggregationOperationState(const AggregationStateSpec 
       spec_.aggregates[a].argument_expression = nullptr;
     }
     const AggregateSpec &ag = spec_.aggregates[a];
+    if (ag.is_distinct && !unary_columns_.empty()) {   // (the distinctify tables are keyed by group-by ATTRIBUTES)
+      throw ExecutionError("DISTINCT aggregate beside a unary group-by key", QSX_ERR_UNSUPPORTED);
+    }
+    if (ag.argument_expression != nullptr && ag.argument_expression->kind == Scalar::kUnaryExpression) {
+      throw ExecutionError("a unary expression as an aggregate's argument: project it with a Select first", QSX_ERR_UNSUPPORTED);
+    }
     if (ag.is_distinct && !interned_.empty()) {   // (finalizeWithDistinct lines its result sets up by sorting on key VALUES)
       throw ExecutionError("DISTINCT aggregate beside a CHAR(n) group-by key that is interned into ids", QSX_ERR_UNSUPPORTED);
     }
@@ -898,8 +1055,8 @@ void AggregationOperationState::internBlocks(std::vector<InternRequest> *request
       std::int32_t *ids = static_cast<std::int32_t *>(scratch->take(static_cast<std::size_t>(n) * 4));
       r.ids[k] = ids;
       if (n == 0) continue;
-      const CompressedAttribute *ca = r.block->compressedAttribute(key.attribute);
-      if (ca != nullptr && ca->kind == CompressedAttribute::kDictionary && !r.block->valuesMaterialized(key.attribute)) {
+      const CompressedAttribute *ca = key.derived ? nullptr : r.block->compressedAttribute(key.attribute);
+      if (!key.derived && ca != nullptr && ca->kind == CompressedAttribute::kDictionary && !r.block->valuesMaterialized(key.attribute)) {
         // (one more entry than codes: the dictionary's NULL code, num_codes, maps to -1)
         coded.push_back(Coded{ca, n, static_cast<std::int32_t *>(scratch->take((static_cast<std::size_t>(ca->num_codes) + 1) * 4)), ids});
         continue;
@@ -913,7 +1070,7 @@ void AggregationOperationState::internBlocks(std::vector<InternRequest> *request
         }
       }
       rows.push_back(n);
-      cols.push_back(r.block->stripe(key.attribute));
+      cols.push_back(key.derived ? r.derived.at(static_cast<std::size_t>(key.column)) : r.block->stripe(key.attribute));
       filters.push_back(filter);
       outs.push_back(ids);
     }
@@ -1058,9 +1215,18 @@ void AggregationOperationState::aggregateBlock(const StorageBlock &block, const 
     }
     cc->evaluator.evalBlock(block, const_cast<void *>(derived[cc->column]), bits);
   }
+  // the unary group-by keys of the block likewise; a key is NULL where its operand is
+  for (const auto &uc : unary_columns_) {
+    const UnaryEvaluator &ev = uc->evaluator;
+    case_scratch.emplace_back(new DeviceBuffer(static_cast<std::size_t>(n) * static_cast<std::size_t>(ev.result.width) + 16));
+    derived[uc->column] = case_scratch.back()->ptr;
+    if (ev.evalBlock(block, case_scratch.back()->ptr, &case_scratch)) ++unary_coded_blocks_;
+    nulls[uc->column] = ev.result.nullable && n > 0 ? block.nullBitmap(ev.operand) : nullptr;
+    any_nulls = any_nulls || nulls[uc->column] != nullptr;
+  }
   int code_width[QSX_MAX_COLUMNS] = {};
   bool any_coded = false;
-  for (std::size_t i = 0; i < column_attr_.size() && !any_nulls && case_columns_.empty(); ++i) {
+  for (std::size_t i = 0; i < column_attr_.size() && !any_nulls && case_columns_.empty() && unary_columns_.empty(); ++i) {
     const CompressedAttribute *ca = block.compressedAttribute(column_attr_[i]);
     const int type = config_.column_type[i];
     if (ca != nullptr && type != kChar && internedKeyOf(i) < 0 && !block.valuesMaterialized(column_attr_[i])) {
@@ -1070,12 +1236,13 @@ void AggregationOperationState::aggregateBlock(const StorageBlock &block, const 
   }
   // the id stripes of the interned CHAR(n) keys stand where the attribute's stripe would (under the filter the update gets)
   InternScratch intern_scratch;
-  std::vector<InternRequest> intern(1, InternRequest{&block, lip_filter, {}});
+  std::vector<InternRequest> intern(1, InternRequest{&block, lip_filter, {}, {}});
+  if (!unary_columns_.empty()) intern[0].derived.assign(derived, derived + QSX_MAX_COLUMNS);
   if (n > 0) internBlocks(&intern, &intern_scratch);
   const auto stripe_of = [&](std::size_t i) -> const void * {
-    if (column_attr_[i] == kInvalidAttributeID) return derived[i];
     const int key = internedKeyOf(i);
-    return key >= 0 && n > 0 ? intern[0].ids[key] : block.stripe(column_attr_[i]);
+    if (key >= 0 && n > 0) return intern[0].ids[key];
+    return column_attr_[i] == kInvalidAttributeID ? derived[i] : block.stripe(column_attr_[i]);
   };
   if (any_coded && n > 0) {
     bool use_coded = false;
@@ -1138,10 +1305,11 @@ void AggregationOperationState::externalizeCodedPredicate() {
   }
 }
 
-// A run of blocks through a state with CASE arguments: the WHEN predicates over the run (RunPredicateMatches), the derived
+// A run of blocks through a state with derived columns — CASE arguments and unary group-by keys.  The unary keys by one
+// _blocks launch each (UnaryEvaluator::evalBlocks), and then, as for the CASE arguments: the WHEN predicates over the run (RunPredicateMatches), the derived
 // columns by one qsx_eval_case_blocks each, one qsx_agg_update_blocks — when no derived column can be NULL (the TPC-H shape:
 // ELSE 0 over non-nullable attributes) and the run forms cover the blocks; otherwise block by block, like nullable attributes.
-void AggregationOperationState::aggregateBlocksWithCase(const std::vector<BlockReference> &blocks,
+void AggregationOperationState::aggregateBlocksWithDerivedColumns(const std::vector<BlockReference> &blocks,
                                                         const std::vector<const std::uint64_t *> &lip_filters) {
   bool in_run = state_ != nullptr && distinctify_.empty() && external_predicate_.conjuncts.empty();
   for (const auto &cc : case_columns_) in_run = in_run && !cc->evaluator.nullable;
@@ -1161,6 +1329,20 @@ void AggregationOperationState::aggregateBlocksWithCase(const std::vector<BlockR
   }
   std::vector<std::unique_ptr<DeviceBuffer>> case_scratch;
   std::vector<std::unique_ptr<RunMatches>> keep;
+  // the unary keys of the run: a key over a nullable operand carries null bitmaps, which travel with single-block calls
+  for (const auto &uc : unary_columns_) {
+    for (const BlockReference &b : run) in_run = in_run && b->nullBitmap(uc->evaluator.operand) == nullptr;
+  }
+  std::vector<std::vector<void *>> unary_derived(unary_columns_.size());
+  std::int64_t on_codes = 0;
+  for (std::size_t k = 0; k < unary_columns_.size() && in_run && !run.empty(); ++k) {
+    const UnaryEvaluator &ev = unary_columns_[k]->evaluator;
+    for (std::int64_t n : rows) {
+      case_scratch.emplace_back(new DeviceBuffer(static_cast<std::size_t>(n) * static_cast<std::size_t>(ev.result.width) + 16));
+      unary_derived[k].push_back(case_scratch.back()->ptr);
+    }
+    on_codes += ev.evalBlocks(run, rows, unary_derived[k].data(), &case_scratch);
+  }
   std::vector<std::vector<void *>> derived(case_columns_.size());
   for (std::size_t k = 0; k < case_columns_.size() && in_run && !run.empty(); ++k) {
     for (std::int64_t n : rows) {
@@ -1178,17 +1360,23 @@ void AggregationOperationState::aggregateBlocksWithCase(const std::vector<BlockR
   InternScratch intern_scratch;
   std::vector<InternRequest> intern;
   if (!interned_.empty()) {
-    for (std::size_t b = 0; b < run.size(); ++b) intern.push_back(InternRequest{run[b].get(), filters[b], {}});
+    for (std::size_t b = 0; b < run.size(); ++b) {
+      intern.push_back(InternRequest{run[b].get(), filters[b], {}, {}});
+      if (unary_columns_.empty()) continue;
+      intern.back().derived.assign(QSX_MAX_COLUMNS, nullptr);
+      for (std::size_t k = 0; k < unary_columns_.size(); ++k) intern.back().derived[static_cast<std::size_t>(unary_columns_[k]->column)] = unary_derived[k][b];
+    }
     internBlocks(&intern, &intern_scratch);
   }
   std::vector<const void *> cols;
   for (std::size_t b = 0; b < run.size(); ++b) {
     for (std::size_t c = 0; c < column_attr_.size(); ++c) {
       const int key = internedKeyOf(c);
-      if (column_attr_[c] == kInvalidAttributeID) {
-        for (std::size_t k = 0; k < case_columns_.size(); ++k) if (static_cast<std::size_t>(case_columns_[k]->column) == c) cols.push_back(derived[k][b]);
-      } else if (key >= 0) {
+      if (key >= 0) {
         cols.push_back(intern[b].ids[static_cast<std::size_t>(key)]);
+      } else if (column_attr_[c] == kInvalidAttributeID) {
+        for (std::size_t k = 0; k < case_columns_.size(); ++k) if (static_cast<std::size_t>(case_columns_[k]->column) == c) cols.push_back(derived[k][b]);
+        for (std::size_t k = 0; k < unary_columns_.size(); ++k) if (static_cast<std::size_t>(unary_columns_[k]->column) == c) cols.push_back(unary_derived[k][b]);
       } else {
         cols.push_back(run[b]->stripe(column_attr_[c]));
       }
@@ -1196,14 +1384,16 @@ void AggregationOperationState::aggregateBlocksWithCase(const std::vector<BlockR
   }
   CheckStatus(qsx_agg_update_blocks(state_, static_cast<int>(rows.size()), rows.data(), cols.data(), any_filter ? filters.data() : nullptr,
                                     CurrentStream()), "qsx_agg_update_blocks");
-  case_run_blocks_ += static_cast<std::int64_t>(rows.size());
+  if (!case_columns_.empty()) case_run_blocks_ += static_cast<std::int64_t>(rows.size());
+  if (!unary_columns_.empty()) unary_run_blocks_ += static_cast<std::int64_t>(rows.size());
+  unary_coded_blocks_ += on_codes;
   CheckStatus(qsx_stream_synchronize(CurrentStream()), "qsx_stream_synchronize");   // the scratch behind the derived columns and bitmaps goes back
 }
 
 void AggregationOperationState::aggregateBlocks(const std::vector<BlockReference> &blocks,
                                                 const std::vector<const std::uint64_t *> &lip_filters) {
-  if (!case_columns_.empty()) {
-    aggregateBlocksWithCase(blocks, lip_filters);
+  if (!case_columns_.empty() || !unary_columns_.empty()) {   // states with derived columns
+    aggregateBlocksWithDerivedColumns(blocks, lip_filters);
     return;
   }
   std::vector<std::int64_t> rows;
@@ -1265,13 +1455,13 @@ void AggregationOperationState::aggregateBlocks(const std::vector<BlockReference
         // a block that compressed an operand differently than the block the coded state was created for (another code width, or
         // not at all): its values — stripe() decodes them once — join the run of plain stripes instead of a call of their own
         rows.push_back(block.numTuples());
-        if (!interned_.empty()) intern.push_back(InternRequest{&block, filter, {}});
+        if (!interned_.empty()) intern.push_back(InternRequest{&block, filter, {}, {}});
         for (std::size_t c = 0; c < column_attr_.size(); ++c) cols.push_back(stripe_or_placeholder(block, c, false, cols.size()));
         filters.push_back(filter);
         any_filter = any_filter || filter != nullptr;
         continue;
       }
-      if (!interned_.empty()) intern.push_back(InternRequest{&block, filter, {}});
+      if (!interned_.empty()) intern.push_back(InternRequest{&block, filter, {}, {}});
       coded_rows.push_back(block.numTuples());
       coded_refs.push_back(blocks[i]);
       for (std::size_t c = 0; c < column_attr_.size(); ++c) {
@@ -1289,7 +1479,7 @@ void AggregationOperationState::aggregateBlocks(const std::vector<BlockReference
       continue;
     }
     rows.push_back(block.numTuples());
-    if (!interned_.empty()) intern.push_back(InternRequest{&block, filter, {}});
+    if (!interned_.empty()) intern.push_back(InternRequest{&block, filter, {}, {}});
     for (std::size_t c = 0; c < column_attr_.size(); ++c) cols.push_back(stripe_or_placeholder(block, c, false, cols.size()));
     filters.push_back(filter);
     any_filter = any_filter || filter != nullptr;

@@ -421,11 +421,13 @@ typedef InsertDestination PartitionAwareInsertDestination;   // (one class: the 
 // (ScalarBinaryExpression.cpp:100-195); TPC-H's DECIMAL columns are DOUBLE in the reference (parser/SqlParser.ypp:791-793).
 // ---------------------------------------------------------------------------
 enum class BinaryOperationID { kAdd = 0, kSubtract, kMultiply, kDivide };
+// the unary operations of types/operations/unary_operations/ that have a device form (qsx_eval_date_extract, qsx_eval_substring)
+enum class UnaryOperationID { kDateExtract = 0, kSubstring };
 class Scalar;
 typedef std::shared_ptr<const Scalar> ScalarPtr;
 class Scalar {
  public:
-  enum Kind { kAttribute, kLiteral, kBinaryExpression, kCaseExpression };
+  enum Kind { kAttribute, kLiteral, kBinaryExpression, kCaseExpression, kUnaryExpression };
   Kind kind = kAttribute;
   attribute_id attribute = kInvalidAttributeID;
   double literal = 0.0;
@@ -443,6 +445,29 @@ class Scalar {
   static ScalarPtr Case(std::vector<std::pair<Predicate, ScalarPtr>> when_then, ScalarPtr else_value) {
     auto s = std::make_shared<Scalar>();
     s->kind = kCaseExpression; s->whens = std::move(when_then); s->else_result = std::move(else_value);
+    return s;
+  }
+  // kUnaryExpression — EXTRACT(YEAR | MONTH FROM operand) (DateExtractOperation.cpp:117-142, 277-286: an INT) and
+  // SUBSTRING(operand FROM start + 1 FOR length) (SubstringOperation.cpp:74-91: CHAR(min(width - start, length)), `start`
+  // 0-based as SubstringOperation::Instance takes it, the text zero-filled to the result's width).  The operand is an
+  // ATTRIBUTE, a DATE or a CHAR(n); the result is nullable exactly when the attribute is.  A unary scalar is the root of a
+  // Select scalar or a group-by key (AggregationStateSpec::group_by_scalars); an EXTRACT may also be a leaf of an arithmetic
+  // tree in a Select scalar (Select.test:688).  Anything else — another operand, a unary in a CASE, as an aggregate's
+  // argument, SUBSTRING inside arithmetic — is QSX_ERR_UNSUPPORTED.  Predicates compare attributes and literals only, so no
+  // unary reaches them.
+  UnaryOperationID unary_operation = UnaryOperationID::kDateExtract;
+  int date_extract_unit = QSX_DATE_YEAR;   // QSX_DATE_YEAR / QSX_DATE_MONTH (any other unit: QSX_ERR_UNSUPPORTED)
+  int substring_start = 0, substring_length = 0;
+  ScalarPtr operand;
+  static ScalarPtr DateExtract(int unit, ScalarPtr date) {
+    auto s = std::make_shared<Scalar>();
+    s->kind = kUnaryExpression; s->unary_operation = UnaryOperationID::kDateExtract; s->date_extract_unit = unit; s->operand = std::move(date);
+    return s;
+  }
+  static ScalarPtr Substring(int start, int length, ScalarPtr text) {
+    auto s = std::make_shared<Scalar>();
+    s->kind = kUnaryExpression; s->unary_operation = UnaryOperationID::kSubstring;
+    s->substring_start = start; s->substring_length = length; s->operand = std::move(text);
     return s;
   }
   static ScalarPtr Attribute(attribute_id a) { auto s = std::make_shared<Scalar>(); s->kind = kAttribute; s->attribute = a; return s; }
@@ -467,13 +492,18 @@ class Scalar {
 // (qsx_eval_expression_long) and, when AggregationStateSpec::integer_argument_arithmetic is set, inside the aggregation kernel
 // (QSX_EX_IADD .. IDIV); without that flag aggregate arguments are evaluated in double (exact below 2^53) and typed DOUBLE.
 TypeID ScalarResultType(const ScalarPtr &scalar, const CatalogRelation &relation);
-// A CASE has the unifying type of its branches (the resolver's Cast, Resolver.cpp:2819-2829).
+// A CASE has the unifying type of its branches (the resolver's Cast, Resolver.cpp:2819-2829).  A unary expression answers
+// kInt (EXTRACT) or kChar (SUBSTRING); UnaryResultType adds the width and the nullability (the operand attribute's).
+Type UnaryResultType(const ScalarPtr &scalar, const CatalogRelation &relation);
 // Scalar trees flattened into one expression program (qsx_expr_instr_t[]): one instruction per distinct binary node —
 // a subexpression shared by several scalars is computed once, the role of the reference's ColumnVectorCache — input
 // attributes mapped to program columns through `column_of`.
 class ExpressionFlattener {
  public:
   explicit ExpressionFlattener(std::function<int(attribute_id)> column_of) : column_of_(std::move(column_of)) {}
+  // An EXTRACT leaf enters the program as one more INT column: `column_of_unary` gives the program column that will hold its
+  // extracted stripe.  Without it (an aggregation state's program, a CASE's) a unary leaf is QSX_ERR_UNSUPPORTED.
+  void acceptDateExtract(std::function<int(const ScalarPtr &)> column_of_unary) { column_of_unary_ = std::move(column_of_unary); }
   // integer_relation != nullptr: a node whose own subtree has ScalarResultType INT / LONG over that relation becomes an
   // integer instruction (QSX_EX_IADD .. IDIV) — also inside a DOUBLE-typed tree, which is what the reference computes for
   // (a + b) * 0.5 with integer a, b.  Otherwise every node is a double instruction.
@@ -484,6 +514,7 @@ class ExpressionFlattener {
   const std::vector<double> &consts() const { return consts_; }
  private:
   std::function<int(attribute_id)> column_of_;
+  std::function<int(const ScalarPtr &)> column_of_unary_;
   const CatalogRelation *integer_relation_ = nullptr;
   std::vector<qsx_expr_instr_t> instrs_;
   std::vector<double> consts_;
@@ -506,6 +537,12 @@ struct AggregateSpec {
 struct AggregationStateSpec {
   const CatalogRelation *input_relation = nullptr;
   std::vector<attribute_id> group_by;
+  // The group-by list as Scalars (AggregationOperationState.cpp:74-130); when non-empty it replaces `group_by`.  Entries are
+  // kAttribute or kUnaryExpression: GROUP BY EXTRACT(YEAR FROM o_orderdate) (TPC-H Q7-Q9), GROUP BY SUBSTRING(c_phone FROM 1
+  // FOR 2) (Q22).  A unary key is a derived column of the state, typed INT or CHAR(m) and treated as an attribute of that type
+  // would be (any strategy for the INT; packed for m = 1, 2, 4, 8, interned otherwise); a NULL operand is a NULL key.  Such a
+  // state has no DISTINCT aggregates and is not exchanged across ranks (QSX_ERR_UNSUPPORTED).
+  std::vector<ScalarPtr> group_by_scalars;
   std::vector<AggregateSpec> aggregates;
   const Predicate *predicate = nullptr;  // the state owns the predicate in the reference (:440-445)
   qsx_agg_strategy_t strategy = QSX_AGG_GENERIC;
@@ -546,6 +583,12 @@ class AggregationOperationState {
   std::int64_t numBlocksAggregatedOnCodes() const { return coded_blocks_.load(); }
   // blocks whose CASE arguments were evaluated by the run form (qsx_eval_case_blocks) and aggregated by one launch over the run
   std::int64_t numBlocksWithCaseEvaluatedInRuns() const { return case_run_blocks_.load(); }
+  // blocks whose unary group-by keys were computed by the run forms (qsx_eval_date_extract_blocks / qsx_eval_substring_blocks)
+  // and aggregated by one launch over the run
+  std::int64_t numBlocksWithUnaryKeysEvaluatedInRuns() const { return unary_run_blocks_.load(); }
+  // blocks whose EXTRACT key was taken from the block's date DICTIONARY (extract over num_codes entries, then the code stripe
+  // mapped through the result) instead of from decoded dates
+  std::int64_t numBlocksWithDateExtractOnCodes() const { return unary_coded_blocks_.load(); }
 
  private:
   AggregationStateSpec spec_;
@@ -570,7 +613,14 @@ class AggregationOperationState {
   struct CaseColumn;
   std::vector<std::shared_ptr<CaseColumn>> case_columns_;
   std::atomic<std::int64_t> case_run_blocks_{0};
-  void aggregateBlocksWithCase(const std::vector<BlockReference> &blocks, const std::vector<const std::uint64_t *> &lip_filters);
+  void aggregateBlocksWithDerivedColumns(const std::vector<BlockReference> &blocks, const std::vector<const std::uint64_t *> &lip_filters);
+  // A unary group-by key (AggregationStateSpec::group_by_scalars) is a derived column too: INT or CHAR(m), nullable exactly
+  // when its operand attribute is (whose null bitmap it takes), computed per block (qsx_eval_date_extract / qsx_eval_substring)
+  // or per run (the _blocks forms) in front of the update.  As with CASE the state does not take the code-stripe state; a
+  // dictionary-coded DATE operand is extracted from its dictionary all the same (UnaryEvaluator).
+  struct UnaryColumn;
+  std::vector<std::shared_ptr<UnaryColumn>> unary_columns_;
+  std::atomic<std::int64_t> unary_run_blocks_{0}, unary_coded_blocks_{0};
   // conjuncts the state's kernel does not evaluate itself (CHAR(n) comparisons, terms beyond QSX_MAX_PRED_TERMS): they are
   // evaluated per block like a SelectOperator's predicate and handed to the update as its filter
   Predicate external_predicate_;
@@ -586,7 +636,8 @@ class AggregationOperationState {
   // exchanged across ranks nor combined with DISTINCT aggregates (which sort on key values).
   struct InternedKey {
     int column = 0;                      // column of config_
-    attribute_id attribute = 0;
+    attribute_id attribute = 0;          // (of a derived key: the operand attribute, whose null bitmap is the key's)
+    bool derived = false;                // a unary key: its stripe comes with the request, not from the block
     int width = 0;
     qsx_char_dict_t *dictionary = nullptr;
     std::int64_t capacity = 0;
@@ -598,6 +649,7 @@ class AggregationOperationState {
     const StorageBlock *block;
     const std::uint64_t *filter;
     std::vector<void *> ids;             // out: one id stripe per interned key (they live in the InternScratch)
+    std::vector<const void *> derived;   // in: per config column the stripe of a derived key (empty: the state has none)
   };
   struct InternScratch;                  // the device buffers behind the id stripes of one call
   void internBlocks(std::vector<InternRequest> *requests, InternScratch *scratch);

@@ -321,6 +321,30 @@ struct CaseEvaluator {
                   std::vector<std::unique_ptr<RunMatches>> *keep) const;
 };
 
+// A Scalar::kUnaryExpression ready to be evaluated (query_context.cpp): EXTRACT over a DATE attribute or SUBSTRING over a
+// CHAR(n) attribute.  QSX_ERR_UNSUPPORTED: an operand that is not an attribute of that type, a unit a Date does not have;
+// QSX_ERR_INVALID_ARGUMENT: a SUBSTRING window the C ABI refuses.
+struct UnaryEvaluator {
+  UnaryEvaluator(const ScalarPtr &scalar, const CatalogRelation &relation);
+  ScalarPtr scalar;
+  attribute_id operand = kInvalidAttributeID;   // the result takes this attribute's null bitmap
+  Type operand_type = Type::Int();
+  Type result = Type::Int();                    // INT or CHAR(m), nullable when the operand is
+  typedef std::vector<std::unique_ptr<DeviceBuffer>> Scratch;
+  // A dictionary-coded DATE that has not been decoded yet is not decoded here either: EXTRACT runs over the block's dictionary
+  // (num_codes entries, and a 0 behind them for the NULL code num_codes, which qsx_decode_codes looks up like any other) and the
+  // code stripe is mapped through the result.  A coded CHAR operand of SUBSTRING goes through stripe(): qsx_decode_codes
+  // knows 4- and 8-byte values only.
+  bool extractsOnCodes(const StorageBlock &block) const;
+  // n results into out_dev, stream-ordered; scratch the device work reads lives in `keep` until the caller has waited.
+  // Returns whether the block's dictionary was used.
+  bool evalBlock(const StorageBlock &block, void *out_dev, Scratch *keep) const;
+  // The same over a run: one _blocks launch for the blocks that present a stripe, the dictionary form block by block.
+  // Returns the number of blocks whose dictionary was used.
+  std::int64_t evalBlocks(const std::vector<BlockReference> &blocks, const std::vector<std::int64_t> &rows, void *const *outs,
+                          Scratch *keep) const;
+};
+
 }  // namespace quickstep
 
 #endif  // QUICKSTEP_GPU_INTERNAL_HPP_

@@ -47,6 +47,9 @@ void AggregationOperationState::mergeAcrossRanks(qsx_comm_t *comm) {
     throw ExecutionError("AggregationOperationState::mergeAcrossRanks: a CHAR(n) group-by key interned into rank-local ids is not exchanged",
                          QSX_ERR_UNSUPPORTED);
   }
+  if (!unary_columns_.empty()) {   // (as with CASE arguments the state is fed per rank; its exchange has not been built)
+    throw ExecutionError("AggregationOperationState::mergeAcrossRanks: a state with a unary group-by key is not exchanged", QSX_ERR_UNSUPPORTED);
+  }
   // The local part first, and its outcome agreed on with the peers (qsx_comm_agree): a rank that fails here must not leave
   // the others inside the merge's collectives.  (The collectives agree on their own scratch the same way, csrc/aggregate.hip.)
   int status = QSX_OK;

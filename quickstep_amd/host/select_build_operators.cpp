@@ -276,18 +276,65 @@ void SelectWorkOrder::executeBlock(block_id input_block_id) {
         null_sources.push_back(kInvalidAttributeID);
         continue;
       }
-      // ScalarBinaryExpression / ScalarLiteral: one fused pass over the operand stripes (qsx_eval_expression)
-      std::vector<attribute_id> attrs;
+      if (scalar->kind == Scalar::kUnaryExpression) {
+        // EXTRACT / SUBSTRING: a derived stripe of the block (n INTs, or n fields of CHAR(m)), then the matching rows like any
+        // expression value; it is NULL where its operand attribute is
+        const UnaryEvaluator evaluator(scalar, block->getRelation());
+        const Type &out_type = out->getRelation().getAttributeType(static_cast<attribute_id>(i));
+        if (out_type.id != evaluator.result.id || out_type.width != evaluator.result.width || (evaluator.result.nullable && !out_type.nullable)) {
+          throw ExecutionError("SelectWorkOrder: the output attribute of EXTRACT is an INT, that of SUBSTRING a CHAR(min(width - start, "
+                               "length)), nullable when the operand is", QSX_ERR_INVALID_ARGUMENT);
+        }
+        expression_values.emplace_back(new DeviceBuffer(static_cast<std::size_t>(n > 0 ? n : 1) * static_cast<std::size_t>(evaluator.result.width) + 16));
+        void *values = expression_values.back()->ptr;
+        evaluator.evalBlock(*block, values, &expression_values);
+        src.push_back(values);
+        widths.push_back(evaluator.result.width);
+        null_sources.push_back(evaluator.operand);
+        continue;
+      }
+      // ScalarBinaryExpression / ScalarLiteral: one fused pass over the operand stripes (qsx_eval_expression).  An EXTRACT leaf
+      // is extracted first and enters the program as one more INT column (Select.test:688: EXTRACT(YEAR ..) * 10000 + ..).
+      std::vector<attribute_id> attrs;                         // program column -> attribute, or kInvalidAttributeID:
+      std::vector<std::pair<int, ScalarPtr>> extract_leaves;   // ... an EXTRACT leaf's column
       ExpressionFlattener flattener([&](attribute_id a) {
         for (std::size_t c = 0; c < attrs.size(); ++c) if (attrs[c] == a) return static_cast<int>(c);
         attrs.push_back(a);
         return static_cast<int>(attrs.size() - 1);
       });
+      flattener.acceptDateExtract([&](const ScalarPtr &leaf) {
+        for (const auto &known : extract_leaves) {
+          if (known.second->date_extract_unit == leaf->date_extract_unit && known.second->operand != nullptr && leaf->operand != nullptr &&
+              known.second->operand->kind == Scalar::kAttribute && leaf->operand->kind == Scalar::kAttribute &&
+              known.second->operand->attribute == leaf->operand->attribute) {
+            return known.first;
+          }
+        }
+        attrs.push_back(kInvalidAttributeID);
+        extract_leaves.emplace_back(static_cast<int>(attrs.size() - 1), leaf);
+        return extract_leaves.back().first;
+      });
       const qsx_operand_t result = flattener.add(scalar);
       const void *cols[QSX_MAX_COLUMNS];
       std::int32_t types[QSX_MAX_COLUMNS];
       if (attrs.size() > QSX_MAX_COLUMNS) throw ExecutionError("SelectWorkOrder: expression over too many attributes", QSX_ERR_UNSUPPORTED);
+      attribute_id nullable_operand = kInvalidAttributeID;     // the value is NULL where an EXTRACT's operand is
+      for (const auto &leaf : extract_leaves) {
+        const UnaryEvaluator evaluator(leaf.second, block->getRelation());
+        expression_values.emplace_back(new DeviceBuffer(static_cast<std::size_t>(n > 0 ? n : 1) * 4 + 16));
+        void *values = expression_values.back()->ptr;
+        evaluator.evalBlock(*block, values, &expression_values);
+        cols[leaf.first] = values;
+        types[leaf.first] = kInt;
+        if (evaluator.result.nullable && block->nullBitmap(evaluator.operand) != nullptr) {
+          if (nullable_operand != kInvalidAttributeID && nullable_operand != evaluator.operand) {
+            throw ExecutionError("SelectWorkOrder: EXTRACT leaves over two nullable attributes in one expression", QSX_ERR_UNSUPPORTED);
+          }
+          nullable_operand = evaluator.operand;
+        }
+      }
       for (std::size_t c = 0; c < attrs.size(); ++c) {
+        if (attrs[c] == kInvalidAttributeID) continue;
         cols[c] = block->stripe(attrs[c]);
         types[c] = block->getRelation().getAttributeType(attrs[c]).id;
       }
@@ -314,7 +361,7 @@ void SelectWorkOrder::executeBlock(block_id input_block_id) {
       }
       src.push_back(expression_values.back()->ptr);
       widths.push_back(value_width);
-      null_sources.push_back(kInvalidAttributeID);
+      null_sources.push_back(nullable_operand);
     }
   } else {
     for (std::size_t i = 0; i < simple_selection_.size(); ++i) {

@@ -15,6 +15,7 @@ DATE = 6   # the reference's 8-byte DateLit {int32 year; uint8 month, day; 2 byt
 EQ, NE, LT, LE, GT, GE = range(6)
 CODE_EQ, CODE_NE, CODE_LT, CODE_GE, CODE_RANGE = range(5)            # qsx_code_cmp_t
 MAX_LIKE_PATTERN = 64                                               # QSX_MAX_LIKE_PATTERN (qsx_select_like)
+DATE_YEAR, DATE_MONTH = 0, 1                                        # QSX_DATE_YEAR / QSX_DATE_MONTH (qsx_eval_date_extract)
 # qsx_agg_strategy_t
 AGG_SINGLE_STATE, AGG_COMPACT_KEY, AGG_COLLISION_FREE, AGG_GENERIC = range(4)
 # qsx_agg_fn_t

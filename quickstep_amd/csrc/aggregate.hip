@@ -41,6 +41,7 @@
 #include "agg_jit.hpp"
 #include "comm.hpp"
 #include "partition.hpp"
+#include "run_table.hpp"
 #include "scan.hpp"
 
 #include <atomic>
@@ -2656,9 +2657,8 @@ static int update_factored(qsx_agg_state *st, const void *const *cols, const voi
     const size_t direct_lds = plan.table_bytes;
     // the flush and the spill path read the whole plan: behind a pointer (a kernarg segment beyond 512 bytes has cost this
     // code base a factor before, DESIGN.md "Kernel arguments")
-    const FactoredArgs *a_dev = static_cast<const FactoredArgs *>(staged_device_buffer(s, sizeof(FactoredArgs)));
-    if (a_dev == nullptr) return QSX_ERR_OUT_OF_MEMORY;
-    rc = staged_upload(s, &a, sizeof(FactoredArgs));
+    const FactoredArgs *a_dev = nullptr;
+    rc = staged_table(s, &a, sizeof(FactoredArgs), &a_dev);
     if (rc != QSX_OK) return rc;
     const int per_cu = factored_workgroups_per_cu(direct_lds);
     const int64_t tiles = (n + kFacDirectTile - 1) / kFacDirectTile;
@@ -3244,10 +3244,8 @@ static int update_run_end_to_end(qsx_agg_state_t *st, int num_blocks, const int6
     }
   }
   first_of_width[4] = static_cast<int>(segments.size() / 3);
-  const size_t table_bytes = segments.size() * sizeof(long long);
-  const long long *segments_dev = static_cast<const long long *>(staged_device_buffer(s, table_bytes));
-  if (segments_dev == nullptr) return QSX_ERR_OUT_OF_MEMORY;
-  rc = staged_upload(s, segments.data(), table_bytes);
+  const long long *segments_dev = nullptr;
+  rc = staged_table(s, segments.data(), segments.size() * sizeof(long long), &segments_dev);
   if (rc != QSX_OK) return rc;
   const unsigned chunks = static_cast<unsigned>(std::min<long long>((widest_segment + kConcatChunk - 1) / kConcatChunk, 64));
   for (int wi = 0; wi < 4; ++wi) {
@@ -3506,8 +3504,6 @@ static int agg_update_blocks(qsx_agg_state_t *st, int num_blocks, const int64_t 
       if (rc != QSX_OK) return rc;
     }
   }
-  long long *dev_table = static_cast<long long *>(staged_device_buffer(s, words * sizeof(long long)));
-  if (dev_table == nullptr) return QSX_ERR_OUT_OF_MEMORY;
   table[0] = kBlockRunMagic;
   table[1] = static_cast<long long>(nb);
   table[2] = static_cast<long long>(off1024);
@@ -3515,16 +3511,11 @@ static int agg_update_blocks(qsx_agg_state_t *st, int num_blocks, const int64_t 
   table[4] = static_cast<long long>(off_rows);
   table[5] = static_cast<long long>(off_cols);
   table[6] = any_filter || prepass ? static_cast<long long>(off_filters) : 0;
-  table[7] = 0;
+  // equal-sized blocks (a relation's blocks all hold the same number of tuples but the last): no search per tile
+  table[7] = run_uniform_tiles(1024, nb, rows.data());
   table[8] = block_dicts != nullptr ? static_cast<long long>(off_dicts) : 0;
-  {   // equal-sized blocks (a relation's blocks all hold the same number of tuples but the last): no search per tile
-    const long long per_block = (rows[0] + 1023) / 1024;
-    bool uniform = per_block > 0;
-    for (size_t b = 0; b + 1 < nb && uniform; ++b) uniform = (rows[b] + 1023) / 1024 == per_block;
-    if (uniform && nb > 1 && (rows[nb - 1] + 1023) / 1024 > per_block) uniform = false;
-    if (uniform) table[7] = per_block;
-  }
-  rc = staged_upload(s, table.data(), words * sizeof(long long));
+  long long *dev_table = nullptr;
+  rc = staged_table(s, table.data(), words * sizeof(long long), &dev_table);
   if (rc != QSX_OK) return rc;
   if (factored) {
     // (one staged table per call and stream: the run table, the kernel's tile index, the dictionary sizes and the plan travel together)

@@ -6,13 +6,11 @@
 // granularity").  A run keeps every block's own stripes / bitmaps where they are and gives the kernel a table to find
 // them: the kernel walks the tiles of the whole run, a tile never straddles two blocks.
 //
-// Table (64-bit words, device memory, read through the kernel's `const __restrict__` argument with workgroup- or
-// wave-uniform indices, i.e. scalar loads):
-//   [0] number of blocks   [1] tiles per block when every block but the last has the same number of tiles, else 0
-//   [2] tiles in the run   [3] 1 when the coding arrays below are present, else 0
-//   then arrays of one word per block:  first_tile[nb + 1] | rows[nb] | in[nb] | filter[nb] | out[nb] | base[nb]
-//   and, for a run of JOIN KEY stripes some of which are compressed (header word 3):  code_width[nb] | dictionary[nb]
-// (in / filter / out are device addresses, 0 = absent; base is a row number added to emitted tuple ids).
+// The table lies in device memory as 64-bit words and is read through the kernel's `const __restrict__` argument with
+// workgroup- or wave-uniform indices, i.e. scalar loads.  run_table.hpp names its words — the header, first_tile[], the
+// per-block arrays rows | in | filter | out | base and, for a run of JOIN KEY stripes some of which are compressed,
+// code_width | dictionary — and builds it on the host (RunTable: the tile index, the standard arrays, words the caller
+// appends, the upload); the accessors below read it by the same names.
 //
 // Coded key stripes (storage/CompressedColumnStoreTupleStorageSubBlock.cpp, CompressedTupleStorageSubBlock.hpp:225-300
 // getAttributeValue): the reference compresses every block on its own — an INT / LONG attribute of one block may lie as
@@ -23,10 +21,9 @@
 #define QSX_CSRC_BLOCK_RUNS_HPP_
 
 #include "device_common.hpp"
+#include "run_table.hpp"
 
 namespace qsx {
-
-constexpr int kRunHeaderWords = 4;
 
 struct RunTile {
   int block;
@@ -50,28 +47,28 @@ __device__ __forceinline__ RunTile run_locate(const long long *__restrict__ tabl
   return RunTile{lo, tile - static_cast<int>(table[kRunHeaderWords + lo])};
 }
 __device__ __forceinline__ long long run_rows(const long long *__restrict__ t, int b) {
-  return t[kRunHeaderWords + (t[0] + 1) + b];
+  return t[QSX_RUN_WORD(t[0], kRunRows, b)];
 }
 template <typename T>
 __device__ __forceinline__ const T *run_in(const long long *__restrict__ t, int b) {
-  return as_global(reinterpret_cast<const T *>(t[kRunHeaderWords + (t[0] + 1) + t[0] + b]));
+  return as_global(reinterpret_cast<const T *>(t[QSX_RUN_WORD(t[0], kRunIn, b)]));
 }
 __device__ __forceinline__ const uint64_t *run_filter(const long long *__restrict__ t, int b) {
-  return as_global(reinterpret_cast<const uint64_t *>(t[kRunHeaderWords + (t[0] + 1) + 2 * t[0] + b]));
+  return as_global(reinterpret_cast<const uint64_t *>(t[QSX_RUN_WORD(t[0], kRunFilter, b)]));
 }
 template <typename T>
 __device__ __forceinline__ T *run_out(const long long *__restrict__ t, int b) {
-  return as_global(reinterpret_cast<T *>(t[kRunHeaderWords + (t[0] + 1) + 3 * t[0] + b]));
+  return as_global(reinterpret_cast<T *>(t[QSX_RUN_WORD(t[0], kRunOut, b)]));
 }
 __device__ __forceinline__ long long run_base(const long long *__restrict__ t, int b) {
-  return t[kRunHeaderWords + (t[0] + 1) + 4 * t[0] + b];
+  return t[QSX_RUN_WORD(t[0], kRunBase, b)];
 }
 __device__ __forceinline__ bool run_has_coding(const long long *__restrict__ t) { return t[3] != 0; }
 __device__ __forceinline__ int run_code_width(const long long *__restrict__ t, int b) {
-  return static_cast<int>(t[kRunHeaderWords + (t[0] + 1) + 5 * t[0] + b]);
+  return static_cast<int>(t[QSX_RUN_WORD(t[0], kRunCodeWidth, b)]);
 }
 __device__ __forceinline__ const void *run_dictionary(const long long *__restrict__ t, int b) {
-  return as_global(reinterpret_cast<const unsigned char *>(t[kRunHeaderWords + (t[0] + 1) + 6 * t[0] + b]));
+  return as_global(reinterpret_cast<const unsigned char *>(t[QSX_RUN_WORD(t[0], kRunDictionary, b)]));
 }
 
 // ---- a tile of a stripe, or of a run of blocks (block_runs.hpp) -----------------------------------------------------------
@@ -139,53 +136,12 @@ __device__ __forceinline__ ProbeTileSource<KeyT> probe_tile_source(const long lo
 }  // namespace qsx
 
 #ifndef __HIPCC_RTC__
-#include <vector>
+#include "common.hpp"
 
 namespace qsx {
 
-// Host side: the table of a run whose tiles hold tile_rows rows.  Returns the number of tiles (0: nothing to do);
-// -1 when the run is too long for 32-bit tile numbers.
-// code_widths != nullptr: a run of key stripes with their coding (code_widths[b] = 0 / 1 / 2 / 4; dictionaries may be nullptr, and
-// so may its entries: truncated values).
-inline long long build_run_table(long long tile_rows, long long num_blocks, const int64_t *rows, const void *const *in,
-                                 const void *const *filters, void *const *out, const int64_t *base,
-                                 std::vector<long long> *table, const int32_t *code_widths = nullptr,
-                                 const void *const *dictionaries = nullptr) {
-  const size_t nb = static_cast<size_t>(num_blocks);
-  table->assign(kRunHeaderWords + (nb + 1) + (code_widths != nullptr ? 7 : 5) * nb, 0);
-  long long *first = table->data() + kRunHeaderWords;
-  long long *t_rows = first + nb + 1, *t_in = t_rows + nb, *t_filter = t_in + nb, *t_out = t_filter + nb, *t_base = t_out + nb;
-  long long tiles = 0, uniform = -1;
-  bool same = true;
-  for (size_t b = 0; b < nb; ++b) {
-    const long long bt = (rows[b] + tile_rows - 1) / tile_rows;
-    first[b] = tiles;
-    tiles += bt;
-    if (b + 1 < nb) {                 // every block but the last
-      if (uniform < 0) uniform = bt;
-      else if (bt != uniform) same = false;
-    } else if (uniform >= 0 && bt > uniform) {
-      same = false;                   // a longer last block would spill into a block that does not exist
-    } else if (uniform < 0) {
-      uniform = bt;                   // a single block
-    }
-    t_rows[b] = rows[b];
-    t_in[b] = static_cast<long long>(reinterpret_cast<uintptr_t>(in[b]));
-    t_filter[b] = filters != nullptr ? static_cast<long long>(reinterpret_cast<uintptr_t>(filters[b])) : 0;
-    t_out[b] = out != nullptr ? static_cast<long long>(reinterpret_cast<uintptr_t>(out[b])) : 0;
-    t_base[b] = base != nullptr ? base[b] : 0;
-    if (code_widths != nullptr) {
-      t_base[nb + b] = code_widths[b];
-      t_base[2 * nb + b] = dictionaries != nullptr ? static_cast<long long>(reinterpret_cast<uintptr_t>(dictionaries[b])) : 0;
-    }
-  }
-  first[nb] = tiles;
-  if (tiles > 0x7FFFFFF0ll) return -1;
-  (*table)[0] = num_blocks;
-  (*table)[1] = (same && uniform > 0) ? uniform : 0;
-  (*table)[2] = tiles;
-  (*table)[3] = code_widths != nullptr ? 1 : 0;
-  return tiles;
+inline int RunTable::upload(void *stream) {
+  return staged_table(static_cast<hipStream_t>(stream), words_.data(), words_.size() * sizeof(long long), &dev_);
 }
 
 }  // namespace qsx

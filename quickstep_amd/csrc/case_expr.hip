@@ -554,32 +554,18 @@ int qsx_eval_case_blocks(int num_columns, const int32_t *types, int num_instrs, 
   }
   if (block_out_null_bitmaps == nullptr && (has_null_branch || block_col_null_bitmaps != nullptr)) return QSX_ERR_INVALID_ARGUMENT;
   if (num_blocks == 0) return QSX_OK;
-  // the run's table: block_runs.hpp's header and first_tile[], rows[], then one pointer set per block
-  const size_t nb = static_cast<size_t>(num_blocks);
+  if (!run_blocks_ok(num_blocks, block_rows, nullptr, block_out)) return QSX_ERR_INVALID_ARGUMENT;
+  if (block_out_null_bitmaps != nullptr && !run_blocks_ok(num_blocks, block_rows, nullptr, reinterpret_cast<const void *const *>(block_out_null_bitmaps))) {
+    return QSX_ERR_INVALID_ARGUMENT;
+  }
+  // the run's table: the tile index of run_table.hpp (run_locate, run_rows work on it), then one pointer set per block
   const int whens = desc->num_whens;
-  std::vector<long long> table(kRunHeaderWords + (nb + 1) + nb + nb * kPtrWords, 0);
-  long long *first = table.data() + kRunHeaderWords, *rows = first + nb + 1, *ptrs = rows + nb;
-  long long tiles = 0, uniform = -1;
-  bool same = true;
-  for (size_t b = 0; b < nb; ++b) {
+  RunTable table;
+  const long long tiles = table.index(kWaveRows, num_blocks, block_rows, kPtrWords);
+  if (tiles < 0) return QSX_ERR_INVALID_ARGUMENT;
+  for (int64_t b = 0; b < num_blocks; ++b) {
     const int64_t r = block_rows[b];
-    if (r < 0 || (r > 0 && block_out[b] == nullptr)) return QSX_ERR_INVALID_ARGUMENT;
-    if (block_out_null_bitmaps != nullptr && r > 0 && block_out_null_bitmaps[b] == nullptr) return QSX_ERR_INVALID_ARGUMENT;
-    const long long bt = (r + kWaveRows - 1) / kWaveRows;
-    first[b] = tiles;
-    tiles += bt;
-    // The `uniform` rule is build_run_table's (block_runs.hpp, the loop over the blocks): run_locate divides by it, so the two
-    // must stay in step — every block but the last has `uniform` tiles, the last no more.
-    if (b + 1 < nb) {
-      if (uniform < 0) uniform = bt;
-      else if (bt != uniform) same = false;
-    } else if (uniform >= 0 && bt > uniform) {
-      same = false;
-    } else if (uniform < 0) {
-      uniform = bt;
-    }
-    rows[b] = r;
-    long long *set = ptrs + b * kPtrWords;
+    long long *set = table.at(kRunIn) + b * kPtrWords;
     set[kPtrOut] = word_of(block_out[b]);
     set[kPtrOutNulls] = block_out_null_bitmaps != nullptr ? word_of(block_out_null_bitmaps[b]) : 0;
     for (int c = 0; c < num_columns; ++c) {
@@ -594,18 +580,11 @@ int qsx_eval_case_blocks(int num_columns, const int32_t *types, int num_instrs, 
       set[kPtrWhens + k] = word_of(bitmap);
     }
   }
-  first[nb] = tiles;
-  if (tiles > 0x7FFFFFF0ll) return QSX_ERR_INVALID_ARGUMENT;
   if (tiles == 0) return QSX_OK;
-  table[0] = num_blocks;
-  table[1] = (same && uniform > 0) ? uniform : 0;
-  table[2] = tiles;
   hipStream_t s = as_stream(stream);
-  const size_t bytes = table.size() * sizeof(long long);
-  const long long *runs_dev = static_cast<const long long *>(staged_device_buffer(s, bytes));
-  if (runs_dev == nullptr) return QSX_ERR_OUT_OF_MEMORY;
-  const int up = staged_upload(s, table.data(), bytes);
+  const int up = table.upload(s);
   if (up != QSX_OK) return up;
+  const long long *runs_dev = table.dev();
   CaseProgram *slot = device_slot<CaseProgram>(s);
   if (slot == nullptr) return QSX_ERR_OUT_OF_MEMORY;
   hipLaunchKernelGGL(store_struct_kernel<CaseProgram>, dim3(1), dim3(64), 0, s, prog, slot);

@@ -486,7 +486,7 @@ int launch_intern(qsx_char_dict *d, const Source &src, hipStream_t s) {
   const Dict view = device_view(d);
   const int tile_rows = tile_rows_for(d->width);
   QSX_HIP_TRY(hipMemsetAsync(d->control, 0, 16, s));
-  const int grid = static_cast<int>(src.tiles < 8 * kCUs ? src.tiles : 8 * kCUs);
+  const int grid = tile_grid(src.tiles);
   const size_t lds = claim_lds_bytes(tile_rows, d->width);
   switch (d->width <= 32 ? (d->width + 7) / 8 : 0) {
     case 1: hipLaunchKernelGGL(claim_kernel<1>, dim3(grid), dim3(kBlock), lds, s, view, src, tile_rows); break;
@@ -629,23 +629,18 @@ int qsx_char_dict_intern_blocks(qsx_char_dict_t *d, int64_t num_blocks, const in
   if (d == nullptr || num_blocks < 0 || (num_blocks > 0 && (block_rows == nullptr || block_cols == nullptr || block_out_ids == nullptr))) {
     return QSX_ERR_INVALID_ARGUMENT;
   }
-  for (int64_t b = 0; b < num_blocks; ++b) {
-    if (block_rows[b] < 0 || (block_rows[b] > 0 && (block_cols[b] == nullptr || block_out_ids[b] == nullptr))) return QSX_ERR_INVALID_ARGUMENT;
-  }
+  if (!run_blocks_ok(num_blocks, block_rows, block_cols, reinterpret_cast<const void *const *>(block_out_ids))) return QSX_ERR_INVALID_ARGUMENT;
   if (num_blocks == 0) return QSX_OK;
   hipStream_t s = as_stream(stream);
   const int tile_rows = tile_rows_for(d->width);
-  std::vector<long long> table;
-  const long long tiles = build_run_table(tile_rows, num_blocks, block_rows, block_cols, reinterpret_cast<const void *const *>(block_filters),
-                                          reinterpret_cast<void *const *>(block_out_ids), nullptr, &table);
+  RunTable table;
+  const long long tiles = table.build(tile_rows, num_blocks, block_rows, block_cols, reinterpret_cast<const void *const *>(block_filters),
+                                      reinterpret_cast<void *const *>(block_out_ids), nullptr);
   if (tiles < 0 || tiles * tile_rows > kMaxPositions) return QSX_ERR_UNSUPPORTED;
   if (tiles == 0) return QSX_OK;
-  const size_t bytes = table.size() * sizeof(long long);
-  const long long *runs_dev = static_cast<const long long *>(staged_device_buffer(s, bytes));
-  if (runs_dev == nullptr) return QSX_ERR_OUT_OF_MEMORY;
-  const int rc = staged_upload(s, table.data(), bytes);
+  const int rc = table.upload(s);
   if (rc != QSX_OK) return rc;
-  const Source src{runs_dev, nullptr, 0, nullptr, nullptr, tiles};
+  const Source src{table.dev(), nullptr, 0, nullptr, nullptr, tiles};
   std::lock_guard<std::mutex> lock(d->mutex);
   return launch_intern(d, src, s);
 }

@@ -48,6 +48,10 @@ inline int grid_for(int64_t work_items, int items_per_block) {
   return static_cast<int>(blocks);
 }
 
+// Grid of a kernel whose workgroups each walk a contiguous range of `tiles` tiles: no more workgroups than tiles, at most
+// 8 per CU.
+inline int tile_grid(int64_t tiles) { return static_cast<int>(tiles < 8 * kCUs ? tiles : 8 * kCUs); }
+
 inline int type_width(int type) {
   switch (type) {
     case QSX_INT: case QSX_FLOAT: return 4;
@@ -175,20 +179,25 @@ static StagedBuffer *staged_buffer_for(hipStream_t stream, size_t bytes) {
   b.capacity = cap;
   return &b;
 }
-// The device address the next staged_upload of this (thread, stream) will fill: tables that hold their own addresses need
-// it before they are complete.
-static void *staged_device_buffer(hipStream_t stream, size_t bytes) {
-  StagedBuffer *b = staged_buffer_for(stream, bytes);
-  return b != nullptr ? b->device : nullptr;
-}
-static int staged_upload(hipStream_t stream, const void *host_src, size_t bytes) {
+static int staged_upload(hipStream_t stream, const void *host_src, size_t bytes, void **dev) {
   StagedBuffer *b = staged_buffer_for(stream, bytes);
   if (b == nullptr) return QSX_ERR_OUT_OF_MEMORY;
   QSX_HIP_TRY(hipEventSynchronize(b->copied));   // the previous copy out of the pinned buffer (a fresh event is complete)
   std::memcpy(b->pinned, host_src, bytes);
   QSX_HIP_TRY(hipMemcpyAsync(b->device, b->pinned, bytes, hipMemcpyHostToDevice, stream));
   QSX_HIP_TRY(hipEventRecord(b->copied, stream));
+  *dev = b->device;
   return QSX_OK;
+}
+// The host table of a call -> *dev, the address its kernels read it at.  ONE table per call and stream: there is one staging
+// buffer per (thread, stream), and a second upload would overwrite the first before the call's kernels have read it.  A
+// call that needs two tables sends them as one, the second behind the first (RunTable::append does that for a run table).
+template <typename T>
+static int staged_table(hipStream_t stream, const void *host_src, size_t bytes, T **dev) {
+  void *at = nullptr;
+  const int rc = staged_upload(stream, host_src, bytes, &at);
+  *dev = static_cast<T *>(at);
+  return rc;
 }
 
 // Device scratch of ONE API call.  The stream-ordered allocator (hipMallocAsync / hipFreeAsync) is not used for it: on this

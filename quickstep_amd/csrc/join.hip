@@ -1201,37 +1201,31 @@ static int join_key_pack_blocks_impl(int ncols, const int32_t *types, int64_t nu
   }
   if (total == 0) return QSX_OK;
   if (out_dev == nullptr) return QSX_ERR_INVALID_ARGUMENT;
-  std::vector<long long> table;
-  const long long tiles = build_run_table(512, num_blocks, block_rows, none.data(), nullptr, nullptr, first.data(), &table);
+  RunTable table;
+  const long long tiles = table.build(512, num_blocks, block_rows, none.data(), nullptr, nullptr, first.data());
   if (tiles < 0) return QSX_ERR_INVALID_ARGUMENT;
-  const long long cols_offset = static_cast<long long>(table.size());
+  const size_t entries = static_cast<size_t>(num_blocks) * ncols;
+  const long long cols_offset = table.append(entries);
   for (int64_t b = 0; b < num_blocks; ++b) {
     for (int k = 0; k < ncols; ++k) {
       const void *col = block_cols[b * ncols + k];
       if (block_rows[b] > 0 && col == nullptr) return QSX_ERR_INVALID_ARGUMENT;
-      table.push_back(static_cast<long long>(reinterpret_cast<uintptr_t>(col)));
+      table.words()[cols_offset + b * ncols + k] = RunTable::word_of(col);
     }
   }
-  bool coded = false;
-  for (int64_t e = 0; block_code_widths != nullptr && e < num_blocks * ncols; ++e) {
-    const int w = block_code_widths[e];
-    if (w != 0 && w != 1 && w != 2 && w != 4) return QSX_ERR_INVALID_ARGUMENT;
-    coded = coded || w != 0;
-  }
+  bool coded = false;   // (the widths and the dictionaries ride right behind the columns, where the kernel looks for them)
+  if (block_code_widths != nullptr && !run_code_widths_ok(num_blocks * ncols, block_code_widths, nullptr, &coded)) return QSX_ERR_INVALID_ARGUMENT;
   if (coded) {
-    for (int64_t e = 0; e < num_blocks * ncols; ++e) table.push_back(block_code_widths[e]);
-    for (int64_t e = 0; e < num_blocks * ncols; ++e) {
-      const void *d = block_dictionaries != nullptr && block_code_widths[e] != 0 ? block_dictionaries[e] : nullptr;
-      table.push_back(static_cast<long long>(reinterpret_cast<uintptr_t>(d)));
+    const long long widths = table.append(entries), dictionaries = table.append(entries);
+    for (size_t e = 0; e < entries; ++e) {
+      table.words()[widths + e] = block_code_widths[e];
+      table.words()[dictionaries + e] = RunTable::word_of(block_dictionaries != nullptr && block_code_widths[e] != 0 ? block_dictionaries[e] : nullptr);
     }
   }
   hipStream_t s = as_stream(stream);
-  const size_t bytes = table.size() * sizeof(long long);
-  const long long *runs_dev = static_cast<const long long *>(staged_device_buffer(s, bytes));
-  if (runs_dev == nullptr) return QSX_ERR_OUT_OF_MEMORY;
-  const int rc = staged_upload(s, table.data(), bytes);
+  const int rc = table.upload(s);
   if (rc != QSX_OK) return rc;
-  hipLaunchKernelGGL(key_pack_runs_kernel, dim3(grid_for(tiles, kJBlock / kWave)), dim3(kJBlock), 0, s, a, runs_dev, cols_offset, out_dev, coded ? 1 : 0);
+  hipLaunchKernelGGL(key_pack_runs_kernel, dim3(grid_for(tiles, kJBlock / kWave)), dim3(kJBlock), 0, s, a, table.dev(), cols_offset, out_dev, coded ? 1 : 0);
   QSX_CHECK_LAUNCH();
   return QSX_OK;
 }
@@ -1353,12 +1347,7 @@ static int check_key_coding(const qsx_key_coding_t **coding, int64_t num_blocks)
     return QSX_OK;
   }
   bool any = false;
-  for (int64_t b = 0; b < num_blocks; ++b) {
-    const int w = (*coding)->block_code_width[b];
-    if (w != 0 && w != 1 && w != 2 && w != 4) return QSX_ERR_INVALID_ARGUMENT;
-    if (w == 0 && (*coding)->block_dictionaries != nullptr && (*coding)->block_dictionaries[b] != nullptr) return QSX_ERR_INVALID_ARGUMENT;
-    any = any || w != 0;
-  }
+  if (!run_code_widths_ok(num_blocks, (*coding)->block_code_width, (*coding)->block_dictionaries, &any)) return QSX_ERR_INVALID_ARGUMENT;
   if (!any) *coding = nullptr;   // every stripe holds values: the plain run
   return QSX_OK;
 }
@@ -1372,11 +1361,9 @@ static int join_build_blocks_impl(qsx_join_table_t *t, int64_t num_blocks, const
   if (check_key_coding(&coding, num_blocks) != QSX_OK) return QSX_ERR_INVALID_ARGUMENT;
   std::vector<int64_t> base(static_cast<size_t>(num_blocks));
   int64_t total = 0;
+  if (!run_blocks_ok(num_blocks, block_rows, block_keys, nullptr)) return QSX_ERR_INVALID_ARGUMENT;
   for (int64_t b = 0; b < num_blocks; ++b) {
-    if (block_rows[b] < 0 || (block_rows[b] > 0 && block_keys[b] == nullptr) || block_base_tids[b] < 0 ||
-        static_cast<int64_t>(block_base_tids[b]) + block_rows[b] > INT32_MAX) {
-      return QSX_ERR_INVALID_ARGUMENT;
-    }
+    if (block_base_tids[b] < 0 || static_cast<int64_t>(block_base_tids[b]) + block_rows[b] > INT32_MAX) return QSX_ERR_INVALID_ARGUMENT;
     base[b] = block_base_tids[b];
     total += block_rows[b];
   }
@@ -1391,17 +1378,14 @@ static int join_build_blocks_impl(qsx_join_table_t *t, int64_t num_blocks, const
     for (int64_t seen = t->max_tid.load(); seen < last && !t->max_tid.compare_exchange_weak(seen, last);) {}
   }
   hipStream_t s = as_stream(stream);
-  std::vector<long long> table;
-  const long long groups = build_run_table(kBuildTile, num_blocks, block_rows, block_keys,
-                                           reinterpret_cast<const void *const *>(block_filters), nullptr, base.data(), &table,
-                                           coding != nullptr ? coding->block_code_width : nullptr,
-                                           coding != nullptr ? coding->block_dictionaries : nullptr);
+  RunTable table;
+  const long long groups = table.build(kBuildTile, num_blocks, block_rows, block_keys, reinterpret_cast<const void *const *>(block_filters),
+                                       nullptr, base.data(), coding != nullptr ? coding->block_code_width : nullptr,
+                                       coding != nullptr ? coding->block_dictionaries : nullptr);
   if (groups < 0) return QSX_ERR_INVALID_ARGUMENT;
-  const size_t bytes = table.size() * sizeof(long long);
-  const long long *runs_dev = static_cast<const long long *>(staged_device_buffer(s, bytes));
-  if (runs_dev == nullptr) return QSX_ERR_OUT_OF_MEMORY;
-  rc = staged_upload(s, table.data(), bytes);
+  rc = table.upload(s);
   if (rc != QSX_OK) return rc;
+  const long long *runs_dev = table.dev();
   std::shared_lock<std::shared_mutex> lock(t->mutex);
   if (t->dense) {
     const int dgrid = grid_for(groups, kDBlock / kWave);
@@ -1913,8 +1897,6 @@ static int launch_probe(qsx_join_table_t *t, const void *keys, int64_t n, int32_
   return QSX_OK;
 }
 
-// The table of a run of probe blocks on the device (staged_upload: stream-ordered, pinned); *rows_total = rows of the run,
-// *any_filter = some block has a filter.  Tuple ids: block_base_tids[b] + row, or run-global row numbers when it is NULL.
 // The covering array of `view`'s build-side columns for table t (directly addressed), built on first use: returns its entry
 // size (4 / 8 / 16) and sets *cover, or 0 — no build-side column, entries wider than 16 bytes, duplicate build keys, an entry
 // that came out all-ones, QSX_JOIN_COVER=0 — and the probe reads head[] and the stripes.  `view.table` must be on the device
@@ -1968,37 +1950,37 @@ static int cover_for(qsx_join_table *t, const ProjectionView &view, int entry_by
   return entry_bytes;
 }
 
+// The table of a run of probe blocks on the device; *rows_total = rows of the run, *any_filter = some block has a filter.
+// Tuple ids: block_base_tids[b] + row, or run-global row numbers when it is NULL.  extra: a second table of the same call,
+// sent behind the run table; *extra_dev = where it lies.
 static int upload_probe_run(int64_t num_blocks, const int64_t *block_rows, const void *const *block_keys,
                             const int32_t *block_base_tids, const uint64_t *const *block_filters, uint64_t *const *block_out,
                             hipStream_t stream, const long long **runs_dev, int64_t *tiles, int64_t *rows_total, bool *any_filter,
                             const std::vector<long long> *extra = nullptr, const long long **extra_dev = nullptr,
                             const qsx_key_coding_t *coding = nullptr) {
+  if (!run_blocks_ok(num_blocks, block_rows, block_keys, reinterpret_cast<const void *const *>(block_out))) return QSX_ERR_INVALID_ARGUMENT;
   std::vector<int64_t> base(static_cast<size_t>(num_blocks));
   int64_t total = 0;
   *any_filter = false;
   for (int64_t b = 0; b < num_blocks; ++b) {
-    if (block_rows[b] < 0 || (block_rows[b] > 0 && block_keys[b] == nullptr)) return QSX_ERR_INVALID_ARGUMENT;
-    if (block_rows[b] > 0 && block_out != nullptr && block_out[b] == nullptr) return QSX_ERR_INVALID_ARGUMENT;
     base[b] = block_base_tids != nullptr ? block_base_tids[b] : total;
     if (base[b] < 0 || base[b] + block_rows[b] > INT32_MAX) return QSX_ERR_INVALID_ARGUMENT;
     total += block_rows[b];
     if (block_filters != nullptr && block_filters[b] != nullptr) *any_filter = true;
   }
-  std::vector<long long> table;
-  *tiles = build_run_table(kDenseTile, num_blocks, block_rows, block_keys, reinterpret_cast<const void *const *>(block_filters),
-                           reinterpret_cast<void *const *>(block_out), base.data(), &table,
-                           coding != nullptr ? coding->block_code_width : nullptr, coding != nullptr ? coding->block_dictionaries : nullptr);
+  RunTable table;
+  *tiles = table.build(kDenseTile, num_blocks, block_rows, block_keys, reinterpret_cast<const void *const *>(block_filters),
+                       reinterpret_cast<void *const *>(block_out), base.data(),
+                       coding != nullptr ? coding->block_code_width : nullptr, coding != nullptr ? coding->block_dictionaries : nullptr);
   *rows_total = total;
   if (*tiles < 0) return QSX_ERR_INVALID_ARGUMENT;
   if (*tiles == 0) return QSX_OK;
-  // (a second table of the same call rides behind the run table: one staging buffer per thread and stream)
-  const size_t run_words = table.size();
-  if (extra != nullptr) table.insert(table.end(), extra->begin(), extra->end());
-  const size_t bytes = table.size() * sizeof(long long);
-  *runs_dev = static_cast<const long long *>(staged_device_buffer(stream, bytes));
-  if (*runs_dev == nullptr) return QSX_ERR_OUT_OF_MEMORY;
-  if (extra_dev != nullptr) *extra_dev = *runs_dev + run_words;
-  return staged_upload(stream, table.data(), bytes);
+  const long long extra_at = extra != nullptr ? table.append(extra->size(), extra->data()) : 0;
+  const int rc = table.upload(stream);
+  if (rc != QSX_OK) return rc;
+  *runs_dev = table.dev();
+  if (extra_dev != nullptr) *extra_dev = table.dev() + extra_at;
+  return QSX_OK;
 }
 
 namespace qsx {

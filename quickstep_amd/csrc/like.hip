@@ -372,7 +372,7 @@ int qsx_select_like(const void *col_dev, int width, int64_t n, const void *patte
   const LikePattern pat = clean_pattern(pattern, pattern_length);
   const int tile_rows = like_tile_rows(width);
   const int64_t tiles = (n + tile_rows - 1) / tile_rows;
-  const int grid = static_cast<int>(tiles < 8 * kCUs ? tiles : 8 * kCUs);
+  const int grid = tile_grid(tiles);
   hipLaunchKernelGGL(like_kernel, dim3(grid), dim3(kBlock), like_lds_bytes(tile_rows, width), s, static_cast<const unsigned char *>(col_dev),
                      width, n, pat, negate, filter_dev, out_bitmap_dev, reinterpret_cast<unsigned long long *>(out_count_dev), tile_rows);
   QSX_CHECK_LAUNCH();
@@ -389,24 +389,20 @@ int qsx_select_like_blocks(int width, int64_t num_blocks, const int64_t *block_r
   }
   if (pattern_length > QSX_MAX_LIKE_PATTERN) return QSX_ERR_UNSUPPORTED;
   if (num_blocks == 0) return QSX_OK;
-  for (int64_t b = 0; b < num_blocks; ++b) {
-    if (block_rows[b] < 0 || (block_rows[b] > 0 && (block_cols[b] == nullptr || block_out_bitmaps[b] == nullptr))) return QSX_ERR_INVALID_ARGUMENT;
-  }
+  if (!run_blocks_ok(num_blocks, block_rows, block_cols, reinterpret_cast<const void *const *>(block_out_bitmaps))) return QSX_ERR_INVALID_ARGUMENT;
   hipStream_t s = as_stream(stream);
   if (out_counts_dev != nullptr) QSX_HIP_TRY(hipMemsetAsync(out_counts_dev, 0, sizeof(int64_t) * static_cast<size_t>(num_blocks), s));
   const LikePattern pat = clean_pattern(pattern, pattern_length);
   const int tile_rows = like_tile_rows(width);
-  std::vector<long long> table;
-  const long long tiles = build_run_table(tile_rows, num_blocks, block_rows, block_cols, reinterpret_cast<const void *const *>(block_filters),
-                                          reinterpret_cast<void *const *>(block_out_bitmaps), nullptr, &table);
+  RunTable table;
+  const long long tiles = table.build(tile_rows, num_blocks, block_rows, block_cols, reinterpret_cast<const void *const *>(block_filters),
+                                      reinterpret_cast<void *const *>(block_out_bitmaps), nullptr);
   if (tiles < 0) return QSX_ERR_INVALID_ARGUMENT;
   if (tiles == 0) return QSX_OK;
-  const size_t bytes = table.size() * sizeof(long long);
-  const long long *runs_dev = static_cast<const long long *>(staged_device_buffer(s, bytes));
-  if (runs_dev == nullptr) return QSX_ERR_OUT_OF_MEMORY;
-  const int rc = staged_upload(s, table.data(), bytes);
+  const int rc = table.upload(s);
   if (rc != QSX_OK) return rc;
-  const int grid = static_cast<int>(tiles < 8 * kCUs ? tiles : 8 * kCUs);
+  const long long *runs_dev = table.dev();
+  const int grid = tile_grid(tiles);
   hipLaunchKernelGGL(like_runs_kernel, dim3(grid), dim3(kBlock), like_lds_bytes(tile_rows, width), s, runs_dev, width, pat, negate,
                      reinterpret_cast<unsigned long long *>(out_counts_dev), tile_rows);
   QSX_CHECK_LAUNCH();
@@ -458,33 +454,29 @@ int qsx_select_codes_in_set_blocks(int code_width, int64_t num_blocks, const int
   }
   if (code_width != 1 && code_width != 2 && code_width != 4) return QSX_ERR_UNSUPPORTED;
   if (num_blocks == 0) return QSX_OK;
+  if (!run_blocks_ok(num_blocks, block_rows, block_codes, reinterpret_cast<const void *const *>(block_out_bitmaps))) return QSX_ERR_INVALID_ARGUMENT;
   size_t lds = 0;
   for (int64_t b = 0; b < num_blocks; ++b) {
-    if (block_rows[b] < 0 || block_num_codes[b] < 0 || (block_num_codes[b] > 0 && block_sets[b] == nullptr) ||
-        (block_rows[b] > 0 && (block_codes[b] == nullptr || block_out_bitmaps[b] == nullptr))) {
-      return QSX_ERR_INVALID_ARGUMENT;
-    }
+    if (block_num_codes[b] < 0 || (block_num_codes[b] > 0 && block_sets[b] == nullptr)) return QSX_ERR_INVALID_ARGUMENT;
     const size_t set_bytes = static_cast<size_t>((block_num_codes[b] + 63) / 64) * 8;
     if (set_bytes <= static_cast<size_t>(kSetLdsBytes) && set_bytes > lds) lds = set_bytes;
   }
   hipStream_t s = as_stream(stream);
   if (out_counts_dev != nullptr) QSX_HIP_TRY(hipMemsetAsync(out_counts_dev, 0, sizeof(int64_t) * static_cast<size_t>(num_blocks), s));
   const long long tile_rows = code_width == 1 ? set_tile_rows<uint8_t>() : code_width == 2 ? set_tile_rows<uint16_t>() : set_tile_rows<uint32_t>();
-  std::vector<long long> table;
-  const long long tiles = build_run_table(tile_rows, num_blocks, block_rows, block_codes, reinterpret_cast<const void *const *>(block_filters),
-                                          reinterpret_cast<void *const *>(block_out_bitmaps), nullptr, &table);
+  RunTable table;
+  const long long tiles = table.build(tile_rows, num_blocks, block_rows, block_codes, reinterpret_cast<const void *const *>(block_filters),
+                                      reinterpret_cast<void *const *>(block_out_bitmaps), nullptr);
   if (tiles < 0) return QSX_ERR_INVALID_ARGUMENT;
   if (tiles == 0) return QSX_OK;
-  const long long extra = static_cast<long long>(table.size());
+  const long long extra = table.append(2 * static_cast<size_t>(num_blocks));
   for (int64_t b = 0; b < num_blocks; ++b) {
-    table.push_back(static_cast<long long>(reinterpret_cast<uintptr_t>(block_sets[b])));
-    table.push_back(block_num_codes[b]);
+    table.words()[extra + 2 * b] = RunTable::word_of(block_sets[b]);
+    table.words()[extra + 2 * b + 1] = block_num_codes[b];
   }
-  const size_t bytes = table.size() * sizeof(long long);
-  const long long *runs_dev = static_cast<const long long *>(staged_device_buffer(s, bytes));
-  if (runs_dev == nullptr) return QSX_ERR_OUT_OF_MEMORY;
-  const int rc = staged_upload(s, table.data(), bytes);
+  const int rc = table.upload(s);
   if (rc != QSX_OK) return rc;
+  const long long *runs_dev = table.dev();
   const int grid = grid_for(tiles, 1);
   unsigned long long *counts = reinterpret_cast<unsigned long long *>(out_counts_dev);
   switch (code_width) {

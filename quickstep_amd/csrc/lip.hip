@@ -338,7 +338,7 @@ int qsx_lip_probe(const qsx_lip_filter_t *f, int key_type, const void *keys_dev,
   } else {
     constexpr int RG = 8;    // 2048-row tiles, 8 workgroups per CU (4 and 8 rows per thread measure alike, 16 is 10 % slower)
     const int64_t tiles = (n + RG * kLBlock - 1) / (RG * kLBlock);
-    const int grid = static_cast<int>(tiles < 8 * kCUs ? tiles : 8 * kCUs);
+    const int grid = tile_grid(tiles);
     if (key_type == QSX_INT) {
       hipLaunchKernelGGL((lip_probe_kernel<int32_t, RG, false>), dim3(grid), dim3(kLBlock), 0, s, f->view(),
                          static_cast<const int32_t *>(keys_dev), n, in_bitmap_dev, out_bitmap_dev, count);
@@ -351,34 +351,20 @@ int qsx_lip_probe(const qsx_lip_filter_t *f, int key_type, const void *keys_dev,
   return QSX_OK;
 }
 
-// The table of a run (block_runs.hpp) on the device; *tiles = its tile count (0: nothing to do).
+// The table of a run (block_runs.hpp) on the device; *tiles = its tile count (0: nothing to do, the table stays on the host).
 static int upload_lip_run(long long tile_rows, int64_t num_blocks, const int64_t *block_rows, const void *const *block_keys,
-                          const uint64_t *const *block_in, uint64_t *const *block_out, hipStream_t s, const long long **runs_dev,
+                          const uint64_t *const *block_in, uint64_t *const *block_out, hipStream_t s, RunTable *table,
                           long long *tiles, const qsx_key_coding_t *coding = nullptr) {
   const int32_t *code_widths = coding != nullptr ? coding->block_code_width : nullptr;
   bool any_coded = false;
-  for (int64_t b = 0; b < num_blocks && code_widths != nullptr; ++b) {
-    const int w = code_widths[b];
-    if (w != 0 && w != 1 && w != 2 && w != 4) return QSX_ERR_INVALID_ARGUMENT;
-    if (w == 0 && coding->block_dictionaries != nullptr && coding->block_dictionaries[b] != nullptr) return QSX_ERR_INVALID_ARGUMENT;
-    any_coded = any_coded || w != 0;
-  }
+  if (code_widths != nullptr && !run_code_widths_ok(num_blocks, code_widths, coding->block_dictionaries, &any_coded)) return QSX_ERR_INVALID_ARGUMENT;
   if (!any_coded) code_widths = nullptr;   // every stripe holds values: the plain run
-  for (int64_t b = 0; b < num_blocks; ++b) {
-    if (block_rows[b] < 0 || (block_rows[b] > 0 && (block_keys[b] == nullptr || (block_out != nullptr && block_out[b] == nullptr)))) {
-      return QSX_ERR_INVALID_ARGUMENT;
-    }
-  }
-  std::vector<long long> table;
-  *tiles = build_run_table(tile_rows, num_blocks, block_rows, block_keys, reinterpret_cast<const void *const *>(block_in),
-                           reinterpret_cast<void *const *>(block_out), nullptr, &table, code_widths,
-                           code_widths != nullptr ? coding->block_dictionaries : nullptr);
+  if (!run_blocks_ok(num_blocks, block_rows, block_keys, reinterpret_cast<const void *const *>(block_out))) return QSX_ERR_INVALID_ARGUMENT;
+  *tiles = table->build(tile_rows, num_blocks, block_rows, block_keys, reinterpret_cast<const void *const *>(block_in),
+                        reinterpret_cast<void *const *>(block_out), nullptr, code_widths,
+                        code_widths != nullptr ? coding->block_dictionaries : nullptr);
   if (*tiles < 0) return QSX_ERR_INVALID_ARGUMENT;
-  if (*tiles == 0) return QSX_OK;
-  const size_t bytes = table.size() * sizeof(long long);
-  *runs_dev = static_cast<const long long *>(staged_device_buffer(s, bytes));
-  if (*runs_dev == nullptr) return QSX_ERR_OUT_OF_MEMORY;
-  return staged_upload(s, table.data(), bytes);
+  return *tiles == 0 ? QSX_OK : table->upload(s);
 }
 
 static int lip_build_blocks_impl(qsx_lip_filter_t *f, int key_type, int64_t num_blocks, const int64_t *block_rows,
@@ -388,10 +374,11 @@ static int lip_build_blocks_impl(qsx_lip_filter_t *f, int key_type, int64_t num_
   if (f == nullptr || num_blocks < 0 || (num_blocks > 0 && (block_rows == nullptr || block_keys == nullptr))) return QSX_ERR_INVALID_ARGUMENT;
   if (key_type != QSX_INT && key_type != QSX_LONG) return QSX_ERR_UNSUPPORTED;
   hipStream_t s = as_stream(stream);
-  const long long *runs_dev = nullptr;
+  RunTable table;
   long long groups = 0;
-  const int rc = upload_lip_run(8 * kWave, num_blocks, block_rows, block_keys, block_filters, nullptr, s, &runs_dev, &groups, coding);
+  const int rc = upload_lip_run(8 * kWave, num_blocks, block_rows, block_keys, block_filters, nullptr, s, &table, &groups, coding);
   if (rc != QSX_OK || groups == 0) return rc;
+  const long long *runs_dev = table.dev();
   const int grid = grid_for(groups, kLBlock / kWave);
   if (key_type == QSX_INT) {
     hipLaunchKernelGGL((lip_build_kernel<int32_t, 8, true>), dim3(grid), dim3(kLBlock), 0, s, f->view(), static_cast<const int32_t *>(nullptr),
@@ -430,11 +417,12 @@ static int lip_probe_blocks_impl(const qsx_lip_filter_t *f, int key_type, int64_
   constexpr int R = 8;
   const long long words32 = (f->cardinality + 31) >> 5;
   const bool in_lds = words32 <= kLipLdsWords && total >= static_cast<int64_t>(kCUs) * 65536;
-  const long long *runs_dev = nullptr;
+  RunTable table;
   long long tiles = 0;
   const int rc = upload_lip_run(static_cast<long long>(R) * (in_lds ? 1024 : kLBlock), num_blocks, block_rows, block_keys, block_in_bitmaps,
-                                block_out_bitmaps, s, &runs_dev, &tiles, coding);
+                                block_out_bitmaps, s, &table, &tiles, coding);
   if (rc != QSX_OK || tiles == 0) return rc;
+  const long long *runs_dev = table.dev();
   if (in_lds) {
     const size_t lds = static_cast<size_t>(words32) * 4;
 #define QSX_LIP_LAUNCH_LDS_RUNS(KeyT)                                                                                 \
@@ -452,7 +440,7 @@ static int lip_probe_blocks_impl(const qsx_lip_filter_t *f, int key_type, int64_
     if (key_type == QSX_INT) QSX_LIP_LAUNCH_LDS_RUNS(int32_t); else QSX_LIP_LAUNCH_LDS_RUNS(int64_t);
 #undef QSX_LIP_LAUNCH_LDS_RUNS
   } else {
-    const int grid = static_cast<int>(tiles < 8 * kCUs ? tiles : 8 * kCUs);
+    const int grid = tile_grid(tiles);
     if (key_type == QSX_INT) {
       hipLaunchKernelGGL((lip_probe_kernel<int32_t, R, false, true>), dim3(grid), dim3(kLBlock), 0, s, f->view(),
                          static_cast<const int32_t *>(nullptr), int64_t{0}, static_cast<const uint64_t *>(nullptr),

@@ -1035,17 +1035,16 @@ int qsx_partition_scatter_blocks(int key_type, int64_t num_blocks, const int64_t
     if (out_cols[c] == nullptr) return QSX_ERR_INVALID_ARGUMENT;
   }
   const int64_t chunk_rows = chunk_rows_for(n);
-  std::vector<long long> table;
-  const long long chunks = build_run_table(chunk_rows, nb, rows.data(), keys.data(), nullptr, nullptr, nullptr, &table);
+  RunTable table;
+  const long long chunks = table.build(chunk_rows, nb, rows.data(), keys.data(), nullptr, nullptr, nullptr);
   if (chunks <= 0) return QSX_ERR_INVALID_ARGUMENT;
-  for (int c = 0; c < ncols; ++c) {   // (ChunkSource::cols_at: right behind the table's five arrays)
-    for (int64_t i = 0; i < nb; ++i) table.push_back(static_cast<long long>(reinterpret_cast<uintptr_t>(block_cols[which[i] * ncols + c])));
+  const long long cols_at = table.append(static_cast<size_t>(ncols * nb));   // (ChunkSource::cols_at: right behind the table's five arrays)
+  for (int c = 0; c < ncols; ++c) {
+    for (int64_t i = 0; i < nb; ++i) table.words()[cols_at + c * nb + i] = RunTable::word_of(block_cols[which[i] * ncols + c]);
   }
-  const size_t bytes = table.size() * sizeof(long long);
-  const long long *runs_dev = static_cast<const long long *>(staged_device_buffer(s, bytes));
-  if (runs_dev == nullptr) return QSX_ERR_OUT_OF_MEMORY;
-  const int rc = staged_upload(s, table.data(), bytes);
+  const int rc = table.upload(s);
   if (rc != QSX_OK) return rc;
+  const long long *runs_dev = table.dev();
   const bool is_pow2 = (num_partitions & (num_partitions - 1)) == 0;
   if (key_type == QSX_INT) {
     return launch_partition_t<ColumnKey<int32_t>, 0>(ColumnKey<int32_t>{nullptr}, n, num_partitions, is_pow2 ? 1 : 0, args, out_offsets_dev,

@@ -427,10 +427,8 @@ int qsx_copy_segments(int64_t num_segments, const void *const *src_dev, void *co
   }
   first_word[5] = table.size();
   if (table.empty()) return QSX_OK;
-  const size_t table_bytes = table.size() * sizeof(long long);
-  const long long *dev_table = static_cast<const long long *>(qsx::staged_device_buffer(s, table_bytes));
-  if (dev_table == nullptr) return QSX_ERR_OUT_OF_MEMORY;
-  const int rc = qsx::staged_upload(s, table.data(), table_bytes);
+  const long long *dev_table = nullptr;
+  const int rc = qsx::staged_table(s, table.data(), table.size() * sizeof(long long), &dev_table);
   if (rc != QSX_OK) return rc;
   for (int g = 0; g < 5; ++g) {
     const long long count = static_cast<long long>(first_word[g + 1] - first_word[g]) / 3;

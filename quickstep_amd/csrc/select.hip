@@ -1431,22 +1431,17 @@ template <typename T, bool kCodes>
 static int sorted_runs(int64_t num_blocks, const int64_t *block_rows, const void *const *block_cols, T literal, int op,
                        const std::vector<long long> &extra_words, const uint64_t *const *block_filters, uint64_t *const *block_out_bitmaps,
                        int64_t *out_counts_dev, hipStream_t s) {
-  for (int64_t b = 0; b < num_blocks; ++b) {
-    if (block_rows[b] < 0 || (block_rows[b] > 0 && (block_cols[b] == nullptr || block_out_bitmaps[b] == nullptr))) return QSX_ERR_INVALID_ARGUMENT;
-  }
+  if (!run_blocks_ok(num_blocks, block_rows, block_cols, reinterpret_cast<const void *const *>(block_out_bitmaps))) return QSX_ERR_INVALID_ARGUMENT;
   if (out_counts_dev != nullptr) QSX_HIP_TRY(hipMemsetAsync(out_counts_dev, 0, sizeof(int64_t) * static_cast<size_t>(num_blocks), s));
-  std::vector<long long> table;
-  const long long tiles = build_run_table(kTileWords * 64, num_blocks, block_rows, block_cols, reinterpret_cast<const void *const *>(block_filters),
-                                          reinterpret_cast<void *const *>(block_out_bitmaps), nullptr, &table);
+  RunTable table;
+  const long long tiles = table.build(kTileWords * 64, num_blocks, block_rows, block_cols, reinterpret_cast<const void *const *>(block_filters),
+                                      reinterpret_cast<void *const *>(block_out_bitmaps), nullptr);
   if (tiles < 0) return QSX_ERR_INVALID_ARGUMENT;
   if (tiles == 0) return QSX_OK;
-  const long long extra = kCodes ? static_cast<long long>(table.size()) : 0;
-  table.insert(table.end(), extra_words.begin(), extra_words.end());
-  const size_t bytes = table.size() * sizeof(long long);
-  const long long *runs_dev = static_cast<const long long *>(staged_device_buffer(s, bytes));
-  if (runs_dev == nullptr) return QSX_ERR_OUT_OF_MEMORY;
-  int rc = staged_upload(s, table.data(), bytes);
+  const long long extra = kCodes ? table.append(extra_words.size(), extra_words.data()) : 0;
+  int rc = table.upload(s);
   if (rc != QSX_OK) return rc;
+  const long long *runs_dev = table.dev();
   CallScratch scratch(s);
   rc = scratch.reserve(sizeof(SortedBounds) * static_cast<size_t>(num_blocks));
   if (rc != QSX_OK) return rc;
@@ -1487,7 +1482,7 @@ int qsx_select_cmp_char(const void *col_dev, int width, int64_t n, int op, const
   const bool direct = width <= 16 && lit.length <= 16 && (reinterpret_cast<uintptr_t>(col_dev) & 3) == 0;
   if (direct) tile_rows = 4096;
   const int64_t tiles = (n + tile_rows - 1) / tile_rows;
-  const int grid = static_cast<int>(tiles < 8 * kCUs ? tiles : 8 * kCUs);
+  const int grid = tile_grid(tiles);
   const size_t lds = direct ? kCharDirectLds : (static_cast<size_t>(tile_rows) * width + 15) / 16 * 16;
   hipLaunchKernelGGL(select_char_kernel, dim3(grid), dim3(kBlock), lds, s, static_cast<const unsigned char *>(col_dev), width, n, op,
                      lit, filter_dev, out_bitmap_dev, reinterpret_cast<unsigned long long *>(out_count_dev), tile_rows);
@@ -1505,9 +1500,7 @@ int qsx_select_cmp_char_blocks(int width, int64_t num_blocks, const int64_t *blo
   }
   if (literal_length > QSX_MAX_CHAR_LITERAL) return QSX_ERR_UNSUPPORTED;
   if (num_blocks == 0) return QSX_OK;
-  for (int64_t b = 0; b < num_blocks; ++b) {
-    if (block_rows[b] < 0 || (block_rows[b] > 0 && (block_cols[b] == nullptr || block_out_bitmaps[b] == nullptr))) return QSX_ERR_INVALID_ARGUMENT;
-  }
+  if (!run_blocks_ok(num_blocks, block_rows, block_cols, reinterpret_cast<const void *const *>(block_out_bitmaps))) return QSX_ERR_INVALID_ARGUMENT;
   hipStream_t s = as_stream(stream);
   if (out_counts_dev != nullptr) QSX_HIP_TRY(hipMemsetAsync(out_counts_dev, 0, sizeof(int64_t) * static_cast<size_t>(num_blocks), s));
   CharLiteral lit{};
@@ -1522,17 +1515,15 @@ int qsx_select_cmp_char_blocks(int width, int64_t num_blocks, const int64_t *blo
   bool direct = width <= 16 && lit.length <= 16;
   for (int64_t b = 0; b < num_blocks && direct; ++b) direct = (reinterpret_cast<uintptr_t>(block_cols[b]) & 3) == 0;
   if (direct) tile_rows = 4096;
-  std::vector<long long> table;
-  const long long tiles = build_run_table(tile_rows, num_blocks, block_rows, block_cols, reinterpret_cast<const void *const *>(block_filters),
-                                          reinterpret_cast<void *const *>(block_out_bitmaps), nullptr, &table);
+  RunTable table;
+  const long long tiles = table.build(tile_rows, num_blocks, block_rows, block_cols, reinterpret_cast<const void *const *>(block_filters),
+                                      reinterpret_cast<void *const *>(block_out_bitmaps), nullptr);
   if (tiles < 0) return QSX_ERR_INVALID_ARGUMENT;
   if (tiles == 0) return QSX_OK;
-  const size_t bytes = table.size() * sizeof(long long);
-  const long long *runs_dev = static_cast<const long long *>(staged_device_buffer(s, bytes));
-  if (runs_dev == nullptr) return QSX_ERR_OUT_OF_MEMORY;
-  const int rc = staged_upload(s, table.data(), bytes);
+  const int rc = table.upload(s);
   if (rc != QSX_OK) return rc;
-  const int grid = static_cast<int>(tiles < 8 * kCUs ? tiles : 8 * kCUs);
+  const long long *runs_dev = table.dev();
+  const int grid = tile_grid(tiles);
   const size_t lds = direct ? kCharDirectLds : (static_cast<size_t>(tile_rows) * width + 15) / 16 * 16;
   hipLaunchKernelGGL(select_char_runs_kernel, dim3(grid), dim3(kBlock), lds, s, runs_dev, width, op, lit,
                      reinterpret_cast<unsigned long long *>(out_counts_dev), tile_rows);
@@ -1570,13 +1561,9 @@ int qsx_select_cmp_blocks(int type, int64_t num_blocks, const int64_t *block_row
       (num_blocks > 0 && (block_rows == nullptr || block_cols == nullptr || block_out_bitmaps == nullptr))) {
     return QSX_ERR_INVALID_ARGUMENT;
   }
+  if (!run_blocks_ok(num_blocks, block_rows, block_cols, reinterpret_cast<const void *const *>(block_out_bitmaps))) return QSX_ERR_INVALID_ARGUMENT;
   bool aligned = true;
-  for (int64_t b = 0; b < num_blocks; ++b) {
-    if (block_rows[b] < 0 || (block_rows[b] > 0 && (block_cols[b] == nullptr || block_out_bitmaps[b] == nullptr))) {
-      return QSX_ERR_INVALID_ARGUMENT;
-    }
-    aligned = aligned && aligned16(block_cols[b]);
-  }
+  for (int64_t b = 0; b < num_blocks; ++b) aligned = aligned && aligned16(block_cols[b]);
   hipStream_t s = as_stream(stream);
   if (num_blocks == 0) return QSX_OK;
   if (!aligned) {
@@ -1591,17 +1578,14 @@ int qsx_select_cmp_blocks(int type, int64_t num_blocks, const int64_t *block_row
   if (out_counts_dev != nullptr) QSX_HIP_TRY(hipMemsetAsync(out_counts_dev, 0, sizeof(int64_t) * static_cast<size_t>(num_blocks), s));
   constexpr int kLoadsPerTile = 4;                                   // R of select_packed_runs_kernel
   const long long tile_rows = static_cast<long long>(kWave) * (16 / width) * kLoadsPerTile;
-  std::vector<long long> table;
-  const long long tiles = build_run_table(tile_rows, num_blocks, block_rows, block_cols,
-                                          reinterpret_cast<const void *const *>(block_filters),
-                                          reinterpret_cast<void *const *>(block_out_bitmaps), nullptr, &table);
+  RunTable table;
+  const long long tiles = table.build(tile_rows, num_blocks, block_rows, block_cols, reinterpret_cast<const void *const *>(block_filters),
+                                      reinterpret_cast<void *const *>(block_out_bitmaps), nullptr);
   if (tiles < 0) return QSX_ERR_INVALID_ARGUMENT;
   if (tiles == 0) return QSX_OK;
-  const size_t bytes = table.size() * sizeof(long long);
-  const long long *runs_dev = static_cast<const long long *>(staged_device_buffer(s, bytes));
-  if (runs_dev == nullptr) return QSX_ERR_OUT_OF_MEMORY;
-  const int rc = staged_upload(s, table.data(), bytes);
+  const int rc = table.upload(s);
   if (rc != QSX_OK) return rc;
+  const long long *runs_dev = table.dev();
   switch (type) {
     case QSX_INT: return dispatch_select_runs<int32_t>(op, runs_dev, tiles, literal, out_counts_dev, s);
     case QSX_LONG: return dispatch_select_runs<int64_t>(op, runs_dev, tiles, literal, out_counts_dev, s);
@@ -1729,12 +1713,10 @@ int qsx_select_codes_blocks(int code_width, int64_t num_blocks, const int64_t *b
   }
   if (code_width != 1 && code_width != 2 && code_width != 4) return QSX_ERR_UNSUPPORTED;
   if (num_blocks == 0) return QSX_OK;
+  if (!run_blocks_ok(num_blocks, block_rows, block_codes, reinterpret_cast<const void *const *>(block_out_bitmaps))) return QSX_ERR_INVALID_ARGUMENT;
   bool aligned = true;
   for (int64_t b = 0; b < num_blocks; ++b) {
-    if (block_rows[b] < 0 || (block_rows[b] > 0 && (block_codes[b] == nullptr || block_out_bitmaps[b] == nullptr)) ||
-        block_ops[b] < QSX_CODE_EQ || block_ops[b] > QSX_CODE_RANGE) {
-      return QSX_ERR_INVALID_ARGUMENT;
-    }
+    if (block_ops[b] < QSX_CODE_EQ || block_ops[b] > QSX_CODE_RANGE) return QSX_ERR_INVALID_ARGUMENT;
     aligned = aligned && aligned16(block_codes[b]);
   }
   if (!aligned) {   // a stripe that does not start on a 16-byte boundary takes the row-per-lane kernel: block by block
@@ -1750,25 +1732,24 @@ int qsx_select_codes_blocks(int code_width, int64_t num_blocks, const int64_t *b
   if (out_counts_dev != nullptr) QSX_HIP_TRY(hipMemsetAsync(out_counts_dev, 0, sizeof(int64_t) * static_cast<size_t>(num_blocks), s));
   constexpr int kLoadsPerTile = 4;                                   // R of select_packed_runs_kernel
   const long long tile_rows = static_cast<long long>(kWave) * (16 / code_width) * kLoadsPerTile;
-  std::vector<long long> table;
-  const long long tiles = build_run_table(tile_rows, num_blocks, block_rows, block_codes, reinterpret_cast<const void *const *>(block_filters),
-                                          reinterpret_cast<void *const *>(block_out_bitmaps), nullptr, &table);
+  RunTable table;
+  const long long tiles = table.build(tile_rows, num_blocks, block_rows, block_codes, reinterpret_cast<const void *const *>(block_filters),
+                                      reinterpret_cast<void *const *>(block_out_bitmaps), nullptr);
   if (tiles < 0) return QSX_ERR_INVALID_ARGUMENT;
   if (tiles == 0) return QSX_OK;
-  const long long extra = static_cast<long long>(table.size());
+  const long long extra = table.append(3 * static_cast<size_t>(num_blocks));
   for (int64_t b = 0; b < num_blocks; ++b) {   // the comparison as a code range [lo, hi), != as its complement (as qsx_select_codes)
     const int op = block_ops[b];
     const unsigned long long first = block_first[b], second = block_second[b];
-    table.push_back(static_cast<long long>(op == QSX_CODE_LT ? 0ull : first));
-    table.push_back(static_cast<long long>((op == QSX_CODE_EQ || op == QSX_CODE_NE) ? first + 1 : op == QSX_CODE_LT ? first
-                                           : op == QSX_CODE_GE ? (1ull << 32) : second));
-    table.push_back(op == QSX_CODE_NE ? 1 : 0);
+    long long *range = table.words() + extra + 3 * b;
+    range[0] = static_cast<long long>(op == QSX_CODE_LT ? 0ull : first);
+    range[1] = static_cast<long long>((op == QSX_CODE_EQ || op == QSX_CODE_NE) ? first + 1 : op == QSX_CODE_LT ? first
+                                      : op == QSX_CODE_GE ? (1ull << 32) : second);
+    range[2] = op == QSX_CODE_NE ? 1 : 0;
   }
-  const size_t bytes = table.size() * sizeof(long long);
-  const long long *runs_dev = static_cast<const long long *>(staged_device_buffer(s, bytes));
-  if (runs_dev == nullptr) return QSX_ERR_OUT_OF_MEMORY;
-  const int rc = staged_upload(s, table.data(), bytes);
+  const int rc = table.upload(s);
   if (rc != QSX_OK) return rc;
+  const long long *runs_dev = table.dev();
   const int grid = grid_for(tiles, kWavesPerBlock);
   unsigned long long *counts = reinterpret_cast<unsigned long long *>(out_counts_dev);
   switch (code_width) {
@@ -1979,35 +1960,33 @@ int qsx_compact_gather_blocks(int ncols, const int32_t *widths, int64_t num_bloc
   hipStream_t s = as_stream(stream);
   std::vector<int64_t> base(static_cast<size_t>(num_blocks));
   int64_t total = 0;
+  if (!run_blocks_ok(num_blocks, block_rows, reinterpret_cast<const void *const *>(block_bitmaps), nullptr)) return QSX_ERR_INVALID_ARGUMENT;
   for (int64_t b = 0; b < num_blocks; ++b) {
-    if (block_rows[b] < 0 || (block_rows[b] > 0 && block_bitmaps[b] == nullptr)) return QSX_ERR_INVALID_ARGUMENT;
     base[b] = block_base_tids != nullptr ? block_base_tids[b] : total;
     if (out_tids_dev != nullptr && (base[b] < 0 || base[b] + block_rows[b] > INT32_MAX)) return QSX_ERR_INVALID_ARGUMENT;
     total += block_rows[b];
   }
   if (workspace_bytes < qsx_compact_blocks_workspace_bytes(num_blocks, block_rows)) return QSX_ERR_CAPACITY;
-  std::vector<long long> table;
+  RunTable table;
   std::vector<const void *> no_input(static_cast<size_t>(num_blocks), nullptr);
-  const long long tiles = build_run_table(kTileWords * 64, num_blocks, block_rows, no_input.data(),
-                                          reinterpret_cast<const void *const *>(block_bitmaps), nullptr, base.data(), &table);
+  const long long tiles = table.build(kTileWords * 64, num_blocks, block_rows, no_input.data(),
+                                      reinterpret_cast<const void *const *>(block_bitmaps), nullptr, base.data());
   if (tiles < 0) return QSX_ERR_INVALID_ARGUMENT;
   if (tiles == 0) {
     if (out_count_dev != nullptr) QSX_HIP_TRY(hipMemsetAsync(out_count_dev, 0, sizeof(int64_t), s));
     return QSX_OK;
   }
-  const long long cols_offset = static_cast<long long>(table.size());
+  const long long cols_offset = table.append(static_cast<size_t>(num_blocks) * ncols);
   for (int64_t b = 0; b < num_blocks; ++b) {
     for (int c = 0; c < ncols; ++c) {
       const void *col = block_cols[b * ncols + c];
       if (block_rows[b] > 0 && col == nullptr) return QSX_ERR_INVALID_ARGUMENT;
-      table.push_back(static_cast<long long>(reinterpret_cast<uintptr_t>(col)));
+      table.words()[cols_offset + b * ncols + c] = RunTable::word_of(col);
     }
   }
-  const size_t bytes = table.size() * sizeof(long long);
-  const long long *runs_dev = static_cast<const long long *>(staged_device_buffer(s, bytes));
-  if (runs_dev == nullptr) return QSX_ERR_OUT_OF_MEMORY;
-  const int rc = staged_upload(s, table.data(), bytes);
+  const int rc = table.upload(s);
   if (rc != QSX_OK) return rc;
+  const long long *runs_dev = table.dev();
   int64_t *tile_offsets = static_cast<int64_t *>(workspace_dev);
   int32_t *tile_counts = reinterpret_cast<int32_t *>(static_cast<char *>(workspace_dev) + align_up(sizeof(int64_t) * (tiles + 1), 256));
   hipLaunchKernelGGL(tile_count_runs_kernel, dim3(grid_for(tiles, kWavesPerBlock)), dim3(kBlock), 0, s, runs_dev, tile_counts);
@@ -2064,10 +2043,8 @@ static int upload_segment_table(int num_segments, const void *const *ptrs, const
     first[i] = static_cast<int32_t>(first_row[i]);
     table[first_words + i] = static_cast<long long>(reinterpret_cast<uintptr_t>(ptrs[i]));
   }
-  const size_t bytes = table.size() * sizeof(long long);
-  const long long *dev = static_cast<const long long *>(staged_device_buffer(stream, bytes));
-  if (dev == nullptr) return QSX_ERR_OUT_OF_MEMORY;
-  const int rc = staged_upload(stream, table.data(), bytes);
+  const long long *dev = nullptr;
+  const int rc = staged_table(stream, table.data(), table.size() * sizeof(long long), &dev);
   if (rc != QSX_OK) return rc;
   *first_dev = reinterpret_cast<const int32_t *>(dev);
   *ptrs_dev = dev + first_words;

@@ -226,23 +226,18 @@ int qsx_eval_date_extract_blocks(int unit, int64_t num_blocks, const int64_t *bl
   if (num_blocks < 0 || (num_blocks > 0 && (block_rows == nullptr || block_cols == nullptr || block_out == nullptr))) return QSX_ERR_INVALID_ARGUMENT;
   if (unit != QSX_DATE_YEAR && unit != QSX_DATE_MONTH) return QSX_ERR_UNSUPPORTED;
   if (num_blocks == 0) return QSX_OK;
+  if (!run_blocks_ok(num_blocks, block_rows, block_cols, reinterpret_cast<const void *const *>(block_out))) return QSX_ERR_INVALID_ARGUMENT;
   for (int64_t b = 0; b < num_blocks; ++b) {
-    if (block_rows[b] < 0 || (block_rows[b] > 0 && (block_cols[b] == nullptr || block_out[b] == nullptr)) ||
-        !extract_aligned(block_cols[b], block_out[b])) {
-      return QSX_ERR_INVALID_ARGUMENT;
-    }
+    if (!extract_aligned(block_cols[b], block_out[b])) return QSX_ERR_INVALID_ARGUMENT;
   }
   hipStream_t s = as_stream(stream);
-  std::vector<long long> table;
-  const long long tiles = build_run_table(kExtractTileRows, num_blocks, block_rows, block_cols, nullptr, reinterpret_cast<void *const *>(block_out),
-                                          nullptr, &table);
+  RunTable table;
+  const long long tiles = table.build(kExtractTileRows, num_blocks, block_rows, block_cols, nullptr, reinterpret_cast<void *const *>(block_out), nullptr);
   if (tiles < 0) return QSX_ERR_INVALID_ARGUMENT;
   if (tiles == 0) return QSX_OK;
-  const size_t bytes = table.size() * sizeof(long long);
-  const long long *runs_dev = static_cast<const long long *>(staged_device_buffer(s, bytes));
-  if (runs_dev == nullptr) return QSX_ERR_OUT_OF_MEMORY;
-  const int rc = staged_upload(s, table.data(), bytes);
+  const int rc = table.upload(s);
   if (rc != QSX_OK) return rc;
+  const long long *runs_dev = table.dev();
   const int grid = grid_for(tiles, 1);
   if (unit == QSX_DATE_YEAR) hipLaunchKernelGGL(date_extract_runs_kernel<QSX_DATE_YEAR>, dim3(grid), dim3(kBlock), 0, s, runs_dev);
   else hipLaunchKernelGGL(date_extract_runs_kernel<QSX_DATE_MONTH>, dim3(grid), dim3(kBlock), 0, s, runs_dev);
@@ -259,7 +254,7 @@ int qsx_eval_substring(const void *col_dev, int width, int64_t n, int start, int
   const int tile_rows = substring_tile_rows(width, m);
   const int in_bytes = image_bytes(tile_rows, width);
   const int64_t tiles = (n + tile_rows - 1) / tile_rows;
-  const int grid = static_cast<int>(tiles < 8 * kCUs ? tiles : 8 * kCUs);
+  const int grid = tile_grid(tiles);
   hipLaunchKernelGGL(substring_kernel, dim3(grid), dim3(kBlock), static_cast<size_t>(in_bytes + image_bytes(tile_rows, m)), s,
                      static_cast<const unsigned char *>(col_dev), width, n, start, m, static_cast<unsigned char *>(out_dev), tile_rows, in_bytes);
   QSX_CHECK_LAUNCH();
@@ -274,23 +269,19 @@ int qsx_eval_substring_blocks(int width, int64_t num_blocks, const int64_t *bloc
     return QSX_ERR_INVALID_ARGUMENT;
   }
   if (num_blocks == 0) return QSX_OK;
-  for (int64_t b = 0; b < num_blocks; ++b) {
-    if (block_rows[b] < 0 || (block_rows[b] > 0 && (block_cols[b] == nullptr || block_out[b] == nullptr))) return QSX_ERR_INVALID_ARGUMENT;
-  }
+  if (!run_blocks_ok(num_blocks, block_rows, block_cols, block_out)) return QSX_ERR_INVALID_ARGUMENT;
   hipStream_t s = as_stream(stream);
   const int m = substring_width(width, start, length);
   const int tile_rows = substring_tile_rows(width, m);
   const int in_bytes = image_bytes(tile_rows, width);
-  std::vector<long long> table;
-  const long long tiles = build_run_table(tile_rows, num_blocks, block_rows, block_cols, nullptr, block_out, nullptr, &table);
+  RunTable table;
+  const long long tiles = table.build(tile_rows, num_blocks, block_rows, block_cols, nullptr, block_out, nullptr);
   if (tiles < 0) return QSX_ERR_INVALID_ARGUMENT;
   if (tiles == 0) return QSX_OK;
-  const size_t bytes = table.size() * sizeof(long long);
-  const long long *runs_dev = static_cast<const long long *>(staged_device_buffer(s, bytes));
-  if (runs_dev == nullptr) return QSX_ERR_OUT_OF_MEMORY;
-  const int rc = staged_upload(s, table.data(), bytes);
+  const int rc = table.upload(s);
   if (rc != QSX_OK) return rc;
-  const int grid = static_cast<int>(tiles < 8 * kCUs ? tiles : 8 * kCUs);
+  const long long *runs_dev = table.dev();
+  const int grid = tile_grid(tiles);
   hipLaunchKernelGGL(substring_runs_kernel, dim3(grid), dim3(kBlock), static_cast<size_t>(in_bytes + image_bytes(tile_rows, m)), s, runs_dev,
                      width, start, m, tile_rows, in_bytes);
   QSX_CHECK_LAUNCH();

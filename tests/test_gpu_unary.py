@@ -98,6 +98,30 @@ def test_date_extract_blocks_gives_the_answers_of_single_calls(capi, dev):
     assert capi.eval_date_extract_blocks(T.DATE_YEAR, []) == []
 
 
+def test_date_extract_blocks_small_then_large_table_on_one_stream(capi, dev):
+    """3 blocks, then 2000 blocks of 1..5 rows (a run table of ~96 KB: beyond the first 64 KiB of the stream's staging
+    buffer, which is regrown between two calls), then 3 blocks again, all on one stream that no call has used before."""
+    raw, aligned, shifted, want = dates(dev)
+    rng = np.random.default_rng(7)
+    small = np.array([0, 700, 705, 1800])
+    large = np.concatenate(([0], np.cumsum(rng.integers(1, 6, size=2000))))
+    runs = []
+    for bounds in (small, large, small + 3):
+        first, last = int(bounds[0]), int(bounds[-1])
+        out = torch.full((last - first + GUARD // 4,), -1, dtype=torch.int32, device=dev)
+        pairs = list(zip(bounds[:-1].tolist(), bounds[1:].tolist()))
+        runs.append((out, first, last, [aligned[a:b] for a, b in pairs], [out[a - first:b - first] for a, b in pairs]))
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream()
+    for out, first, last, blocks, outs in runs:
+        capi.eval_date_extract_blocks(T.DATE_YEAR, blocks, outs=outs, stream=stream)
+    stream.synchronize()
+    for out, a, b, _, _ in runs:
+        got = out.cpu().numpy()
+        assert np.array_equal(got[:b - a], want[T.DATE_YEAR][a:b]), "rows %d..%d" % (a, b)
+        assert np.all(got[b - a:] == -1), "rows behind the output were written"
+
+
 # -------------------------------------------------------------------------------------------------------------- SUBSTRING
 ALPHABET = np.frombuffer(b"ab-0123456789 \x80\xc3\xff", dtype=np.uint8)
 

@@ -170,7 +170,7 @@ int qsx_select_cmp_blocks(int type, int64_t num_blocks, const int64_t *block_row
  * types/operations/comparisons/AsciiStringComparators.hpp:218-251).
  *   col_dev      n values of `width` bytes each (1..255), densely packed (a column-store stripe of a CHAR(width) attribute)
  *   literal      host pointer to literal_length (0..64) bytes; a NUL inside ends the literal
- * Other arguments as qsx_select_cmp.  (TPC-H: c_mktsegment = 'BUILDING', l_shipmode IN (...), ...) */
+ * Other arguments as qsx_select_cmp.  (TPC-H: c_mktsegment = 'BUILDING', ...; l_shipmode IN (...) is qsx_select_in_char.) */
 #define QSX_MAX_CHAR_LITERAL 64
 int qsx_select_cmp_char(const void *col_dev, int width, int64_t n, int op, const void *literal, int literal_length,
                         const uint64_t *filter_dev, uint64_t *out_bitmap_dev, int64_t *out_count_dev, qsx_stream_t stream);
@@ -208,6 +208,54 @@ int qsx_select_like(const void *col_dev, int width, int64_t n, const void *patte
 int qsx_select_like_blocks(int width, int64_t num_blocks, const int64_t *block_rows, const void *const *block_cols,
                            const void *pattern, int pattern_length, int negate, const uint64_t *const *block_filters,
                            uint64_t *const *block_out_bitmaps, int64_t *out_counts_dev, qsx_stream_t stream);
+
+/* K1 with an IN list on a numeric or DATE stripe: out_bitmap[i] = ((col[i] == some literal) XOR negate) [AND filter[i]], in one
+ * pass over the column whatever the number of literals.  The reference's execution layer has no IN node: InValueList::concretize
+ * (query_optimizer/expressions/InValueList.cpp:40-65) builds a disjunction of kEqual comparisons, which
+ * DisjunctionPredicate::getAllMatches (expressions/predicate/DisjunctionPredicate.cpp:109-157) evaluates as one scan per literal
+ * and a union of the matches; NOT IN is NegationPredicate::getAllMatches (expressions/predicate/NegationPredicate.cpp:70-90) over
+ * that disjunction.
+ *   type          as qsx_select_cmp (column and literals share it)
+ *   literals      host array of num_literals (1 .. QSX_MAX_IN_LIST) values of `type`; duplicates are allowed
+ *   negate        0: IN, 1: NOT IN.  Bits at positions >= n of the last word are zero, also under negate.
+ *   Equality is the type's own == (LiteralComparators-inl.hpp:330-370 with the equal functor): NaN is in no list, so NOT IN
+ *   selects it; -0.0 equals 0.0.  A DATE compares by year, month and day.
+ *   NULLs are the caller's: the reference's NOT IN selects a row whose value is NULL (see qsx_bitmap_eval), so the null bitmap
+ *   is ANDed out of the leaf BEFORE a negation, not behind it.
+ * filter / out_bitmap (fully overwritten) / out_count as qsx_select_cmp.  num_literals outside 1..QSX_MAX_IN_LIST, negate not
+ * 0 / 1 or NULL pointers with n > 0: QSX_ERR_INVALID_ARGUMENT.  Over a dictionary stripe (col_dev = dictionary, n = num_codes)
+ * the result is that dictionary's code set for qsx_select_codes_in_set, as for qsx_select_like.  (TPC-H: p_size IN (8 values).)
+ * QSX_ABI_VERSION did not change: a caller detects the capability by the presence of the symbols. */
+#define QSX_MAX_IN_LIST 32
+int qsx_select_in(int type, const void *col_dev, int64_t n, const void *literals, int num_literals, int negate,
+                  const uint64_t *filter_dev, uint64_t *out_bitmap_dev, int64_t *out_count_dev, qsx_stream_t stream);
+
+/* qsx_select_in over a run of blocks in one launch (arguments as qsx_select_cmp_blocks / qsx_select_in): one scan per literal
+ * and SelectWorkOrder in the reference (DisjunctionPredicate.cpp:109-157, SelectOperator.cpp:83-150). */
+int qsx_select_in_blocks(int type, int64_t num_blocks, const int64_t *block_rows, const void *const *block_cols,
+                         const void *literals, int num_literals, int negate, const uint64_t *const *block_filters,
+                         uint64_t *const *block_out_bitmaps, int64_t *out_counts_dev, qsx_stream_t stream);
+
+/* The IN list on a CHAR(width) attribute: a row's bytes are loaded once and compared with every literal.  Equality is that of
+ * AsciiStringUncheckedComparator::strcmpHelper (types/operations/comparisons/AsciiStringComparators.hpp:218-251), as in
+ * qsx_select_cmp_char with QSX_EQ: both sides end at their first NUL or at their maximum length; the disjunction is
+ * InValueList.cpp:40-65 / DisjunctionPredicate.cpp:109-157, the negation NegationPredicate.cpp:70-90.
+ *   literals         host array of num_literals slots of QSX_MAX_CHAR_LITERAL bytes each
+ *   literal_lengths  bytes used of every slot (0 .. 64; more: QSX_ERR_UNSUPPORTED); a NUL inside ends the literal.  A literal
+ *                    longer than `width` equals no field; the empty literal equals the empty text.
+ * Other arguments and errors as qsx_select_in; width outside 1..255: QSX_ERR_INVALID_ARGUMENT.  Over a dictionary stripe
+ * (col_dev = dictionary, width = value_width, n = num_codes) the result is that dictionary's code set for
+ * qsx_select_codes_in_set(_blocks).  (TPC-H: l_shipmode IN ('MAIL', 'SHIP'), p_container IN (...).) */
+int qsx_select_in_char(const void *col_dev, int width, int64_t n, const void *literals, const int32_t *literal_lengths,
+                       int num_literals, int negate, const uint64_t *filter_dev, uint64_t *out_bitmap_dev,
+                       int64_t *out_count_dev, qsx_stream_t stream);
+
+/* qsx_select_in_char over a run of blocks in one launch (arguments as qsx_select_cmp_char_blocks / qsx_select_in_char;
+ * DisjunctionPredicate.cpp:109-157 once per block in the reference). */
+int qsx_select_in_char_blocks(int width, int64_t num_blocks, const int64_t *block_rows, const void *const *block_cols,
+                              const void *literals, const int32_t *literal_lengths, int num_literals, int negate,
+                              const uint64_t *const *block_filters, uint64_t *const *block_out_bitmaps, int64_t *out_counts_dev,
+                              qsx_stream_t stream);
 
 /* A device dictionary of CHAR(width) values: every distinct text gets a dense INT id, so that a CHAR(n) group-by component
  * of any width can be grouped as an INT column (qsx_agg_*) and turned back into bytes at finalize.  Stands in for the key
@@ -381,6 +429,48 @@ int qsx_bitmap_combine(int op, const uint64_t *a_dev, const uint64_t *b_dev, int
                        uint64_t *out_dev, qsx_stream_t stream);
 int qsx_bitmap_count(const uint64_t *bitmap_dev, int64_t n, int64_t *out_count_dev,
                      qsx_stream_t stream);
+
+/* A boolean expression over leaf bitmaps (TupleIdSequences of n bits) in ONE launch: the AND / OR / NOT nodes of a predicate
+ * tree above its comparison leaves.  Replaces the recursion of ConjunctionPredicate::getAllMatches (intersection),
+ * DisjunctionPredicate::getAllMatches (expressions/predicate/DisjunctionPredicate.cpp:109-157: the union of the children's
+ * matches) and NegationPredicate::getAllMatches (expressions/predicate/NegationPredicate.cpp:70-90: the child's matches
+ * inverted inside the filter and the existence map).
+ *   Two-valued, as the reference: a comparison with a NULL operand is not true (LiteralComparators-inl.hpp:330-370), and a
+ *   negation inverts that, so NOT (x = 5) SELECTS a row whose x is NULL.  This is the reference's behaviour, not SQL's
+ *   three-valued logic; a caller gets it by ANDing NOT null into the comparison leaf (null bitmap as one more leaf) below the
+ *   negation.  An IN list is a disjunction of equalities (InValueList.cpp:40-65), so NOT IN selects a NULL test value too.
+ *   program      host array of num_instrs (1 .. QSX_MAX_BOOL_INSTRS) postfix codes: k >= 0 pushes leaf k, QSX_BOOL_AND and
+ *                QSX_BOOL_OR pop two values and push one, QSX_BOOL_NOT replaces the top.  The stack never holds more than
+ *                QSX_MAX_BOOL_DEPTH values and ends with exactly one: the result.
+ *   leaves_dev   host array of num_leaves (1 .. QSX_MAX_BOOL_LEAVES) device pointers to (n+63)/64 words each; a NULL entry is
+ *                the all-zero bitmap (a block without a null bitmap in a run where others have one)
+ *   filter_dev   optional: ANDed into the result once, which equals the reference's short-circuit filtering because leaves
+ *                are pure functions of the row
+ *   out_bitmap_dev  (n+63)/64 words, fully overwritten, bits at positions >= n zero; must not share a byte with the words of a
+ *                   leaf or of the filter (checked: QSX_ERR_INVALID_ARGUMENT)
+ *   out_count_dev   optional, written as by qsx_select_cmp
+ * A program that underflows the stack, leaves more or fewer than one value, names a leaf >= num_leaves, is longer than
+ * QSX_MAX_BOOL_INSTRS or deeper than QSX_MAX_BOOL_DEPTH, or a NULL pointer with n > 0: QSX_ERR_INVALID_ARGUMENT, and nothing is
+ * written.  Without a device: QSX_ERR_NO_DEVICE in front of every other check.  QSX_ABI_VERSION did not change. */
+#define QSX_MAX_BOOL_LEAVES 32
+#define QSX_MAX_BOOL_INSTRS 64
+#define QSX_MAX_BOOL_DEPTH 8
+#define QSX_BOOL_AND (-1)
+#define QSX_BOOL_OR (-2)
+#define QSX_BOOL_NOT (-3)
+int qsx_bitmap_eval(int num_leaves, const uint64_t *const *leaves_dev, int num_instrs, const int32_t *program, int64_t n,
+                    const uint64_t *filter_dev, uint64_t *out_bitmap_dev, int64_t *out_count_dev, qsx_stream_t stream);
+
+/* qsx_bitmap_eval over a run of blocks in one launch: one program, every block its own leaves, filter and output
+ * (DisjunctionPredicate.cpp:109-157 / NegationPredicate.cpp:70-90 once per block and SelectWorkOrder in the reference).
+ *   block_leaves   host array of num_blocks * num_leaves device pointers, leaf k of block b at [b * num_leaves + k]; an entry
+ *                  may be NULL (all zero)
+ *   block_filters  NULL, or host array of device pointers (an entry may be NULL)
+ *   out_counts_dev optional device array of num_blocks int64
+ * Every block's result is byte for byte that of qsx_bitmap_eval on that block alone. */
+int qsx_bitmap_eval_blocks(int num_leaves, int num_instrs, const int32_t *program, int64_t num_blocks, const int64_t *block_rows,
+                           const uint64_t *const *block_leaves, const uint64_t *const *block_filters,
+                           uint64_t *const *block_out_bitmaps, int64_t *out_counts_dev, qsx_stream_t stream);
 
 /* Scratch bytes qsx_compact_gather / qsx_bitmap_to_tids need for n input rows. */
 size_t qsx_compact_workspace_bytes(int64_t n);

@@ -66,6 +66,12 @@ _SIGNATURES = {
     "qsx_select_cmp_char": (_int, [_vp, _int, _i64, _int, C.c_char_p, _int, _vp, _vp, _vp, _vp]),
     "qsx_select_cmp_columns": (_int, [_int, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp]),
     "qsx_select_like": (_int, [_vp, _int, _i64, C.c_char_p, _int, _int, _vp, _vp, _vp, _vp]),
+    "qsx_select_in": (_int, [_int, _vp, _i64, _vp, _int, _int, _vp, _vp, _vp, _vp]),
+    "qsx_select_in_blocks": (_int, [_int, _i64, C.POINTER(_i64), _pp, _vp, _int, _int, _pp, _pp, _vp, _vp]),
+    "qsx_select_in_char": (_int, [_vp, _int, _i64, _vp, C.POINTER(_i32), _int, _int, _vp, _vp, _vp, _vp]),
+    "qsx_select_in_char_blocks": (_int, [_int, _i64, C.POINTER(_i64), _pp, _vp, C.POINTER(_i32), _int, _int, _pp, _pp, _vp, _vp]),
+    "qsx_bitmap_eval": (_int, [_int, _pp, _int, C.POINTER(_i32), _i64, _vp, _vp, _vp, _vp]),
+    "qsx_bitmap_eval_blocks": (_int, [_int, _int, C.POINTER(_i32), _i64, C.POINTER(_i64), _pp, _pp, _pp, _vp, _vp]),
     "qsx_char_dict_create": (_int, [_int, _i64, _pp]),
     "qsx_char_dict_destroy": (_int, [_vp]),
     "qsx_char_dict_clear": (_int, [_vp, _vp]),
@@ -405,6 +411,97 @@ def select_like_blocks(cols, pattern, negate=False, filters=None, stream=None):
     cptr = (C.c_void_p * max(nb, 1))(*[c.data_ptr() if c.numel() else None for c in cols])
     _check(_lib.qsx_select_like_blocks(width, nb, rows, cptr, C.c_char_p(pattern), len(pattern), int(negate), fptr, optr, _ptr(counts),
                                        _stream(stream)), "qsx_select_like_blocks")
+    return outs, counts[:nb]
+
+
+def _in_literals(qt, literals):
+    ctype = C.c_int64 if qt == T.DATE else _C_SCALAR[qt]
+    return (ctype * max(len(literals), 1))(*literals)
+
+
+def _in_char_literals(literals):
+    """bytes objects -> (slots of MAX_CHAR_LITERAL bytes, lengths).  A literal longer than a slot keeps its length, so that the
+    library can refuse it; its bytes are cut."""
+    slots = C.create_string_buffer(max(len(literals), 1) * T.MAX_CHAR_LITERAL)
+    for k, lit in enumerate(literals):
+        cut = bytes(lit)[:T.MAX_CHAR_LITERAL]
+        slots[k * T.MAX_CHAR_LITERAL:k * T.MAX_CHAR_LITERAL + len(cut)] = cut
+    return slots, (C.c_int32 * max(len(literals), 1))(*[len(lit) for lit in literals])
+
+
+def select_in(col, literals, negate=False, filter_bitmap=None, stream=None, qtype=None, want_count=True, out_bitmap=None):
+    """K1 with an IN list (negate: NOT IN) on a numeric / DATE stripe, one pass whatever len(literals) is: (bitmap, count);
+    count is None without want_count.  qtype=T.DATE: col is an int64 tensor of raw DateLit bytes, the literals T.date_raw values."""
+    n = col.numel()
+    qt = qsx_type_of(col) if qtype is None else qtype
+    if out_bitmap is None:
+        out_bitmap = new_bitmap(n, col.device)
+    out_count = torch.zeros(1, dtype=torch.int64, device=col.device) if want_count else None
+    _check(_lib.qsx_select_in(qt, _ptr(col), n, _in_literals(qt, literals), len(literals), int(negate), _ptr(filter_bitmap),
+                              _ptr(out_bitmap), _ptr(out_count), _stream(stream)), "qsx_select_in")
+    return out_bitmap, out_count
+
+
+def select_in_blocks(cols, literals, negate=False, filters=None, stream=None, qtype=None):
+    """select_in over a run of blocks in one launch: (per-block bitmaps, counts int64[nb])."""
+    qt = qsx_type_of(cols[0]) if qtype is None else qtype
+    nb, outs, counts, rows, cptr, optr, fptr = _run_outputs(cols, filters)
+    _check(_lib.qsx_select_in_blocks(qt, nb, rows, cptr, _in_literals(qt, literals), len(literals), int(negate), fptr, optr, _ptr(counts),
+                                     _stream(stream)), "qsx_select_in_blocks")
+    return outs, counts[:nb]
+
+
+def select_in_char(col, literals, negate=False, filter_bitmap=None, stream=None, want_count=True, out_bitmap=None):
+    """The IN list on a CHAR(width) stripe: col is a uint8 tensor of shape (n, width), literals bytes objects.  Over a dictionary
+    stripe the bitmap is that dictionary's code set for select_codes_in_set."""
+    n, width = col.shape
+    assert col.dtype == torch.uint8 and col.is_contiguous()
+    if out_bitmap is None:
+        out_bitmap = new_bitmap(n, col.device)
+    out_count = torch.zeros(1, dtype=torch.int64, device=col.device) if want_count else None
+    slots, lengths = _in_char_literals(literals)
+    _check(_lib.qsx_select_in_char(_ptr(col), width, n, slots, lengths, len(literals), int(negate), _ptr(filter_bitmap), _ptr(out_bitmap),
+                                   _ptr(out_count), _stream(stream)), "qsx_select_in_char")
+    return out_bitmap, out_count
+
+
+def select_in_char_blocks(cols, literals, negate=False, filters=None, stream=None):
+    """select_in_char on the CHAR(width) stripes of a run of blocks: cols = uint8 tensors of shape (n_b, width)."""
+    width = cols[0].shape[1]
+    nb, outs, counts, _, _, optr, fptr = _run_outputs([c[:, 0] for c in cols], filters)
+    rows = (C.c_int64 * max(nb, 1))(*[c.shape[0] for c in cols])
+    cptr = (C.c_void_p * max(nb, 1))(*[c.data_ptr() if c.numel() else None for c in cols])
+    slots, lengths = _in_char_literals(literals)
+    _check(_lib.qsx_select_in_char_blocks(width, nb, rows, cptr, slots, lengths, len(literals), int(negate), fptr, optr, _ptr(counts),
+                                          _stream(stream)), "qsx_select_in_char_blocks")
+    return outs, counts[:nb]
+
+
+def bitmap_eval(leaves, program, n, filter_bitmap=None, stream=None, want_count=True, out_bitmap=None):
+    """A postfix boolean program (leaf index >= 0, T.BOOL_AND / T.BOOL_OR / T.BOOL_NOT) over leaf bitmaps of n bits in one launch;
+    a leaf may be None (all zero).  Returns (bitmap, count); count is None without want_count."""
+    dev = next(t.device for t in list(leaves) + [filter_bitmap, out_bitmap] if t is not None)
+    if out_bitmap is None:
+        out_bitmap = new_bitmap(n, dev)
+    out_count = torch.zeros(1, dtype=torch.int64, device=dev) if want_count else None
+    _check(_lib.qsx_bitmap_eval(len(leaves), _ptr_array(leaves), len(program), (C.c_int32 * max(len(program), 1))(*program), n,
+                                _ptr(filter_bitmap), _ptr(out_bitmap), _ptr(out_count), _stream(stream)), "qsx_bitmap_eval")
+    return out_bitmap, out_count
+
+
+def bitmap_eval_blocks(block_leaves, program, block_rows, device, filters=None, stream=None, out_bitmaps=None):
+    """bitmap_eval over a run of blocks in one launch: block_leaves[b] = the leaves of block b (entries may be None).  Returns
+    (per-block bitmaps, counts int64[nb])."""
+    nb = len(block_rows)
+    num_leaves = len(block_leaves[0]) if nb else 1
+    outs = out_bitmaps if out_bitmaps is not None else [new_bitmap(r, device) for r in block_rows]
+    counts = torch.zeros(max(nb, 1), dtype=torch.int64, device=device)
+    rows = (C.c_int64 * max(nb, 1))(*block_rows)
+    lptr = _ptr_array([leaf for leaves in block_leaves for leaf in leaves])
+    optr = _ptr_array([o if r else None for o, r in zip(outs, block_rows)])
+    fptr = None if filters is None else _ptr_array(filters)
+    _check(_lib.qsx_bitmap_eval_blocks(num_leaves, len(program), (C.c_int32 * max(len(program), 1))(*program), nb, rows, lptr, fptr, optr,
+                                       _ptr(counts), _stream(stream)), "qsx_bitmap_eval_blocks")
     return outs, counts[:nb]
 
 

@@ -1119,14 +1119,57 @@ __device__ __forceinline__ unsigned long long up_to_first_zero_byte(unsigned lon
   const unsigned long long z = (x - 0x0101010101010101ull) & ~x & 0x8080808080808080ull;
   return z != 0ull ? ((z & (0ull - z)) - 1ull) : ~0ull;
 }
-// One tile (rows [row0, row0 + tile_rows) of a stripe) of the CHAR comparison; lane 0 of every wave adds its words' bits to count.
-__device__ __forceinline__ void select_char_tile(const unsigned char *__restrict__ col, int width, int64_t n, int op, const CharLiteral &lit,
+// What select_char_tile tests a row's text against: `text OP literal` here, the IN list of qsx_select_in_char further down.
+//   fits16()             every text that can pass lies in 16 bytes, so fields of width <= 16 may take the register path
+//   key16()              what match16 needs besides the row, made once per tile
+//   match16(key, a, b)   the row's text as two big-endian 64-bit numbers: cut at its first NUL, zero-padded
+//   match(v, width)      the row's `width` bytes in LDS
+struct CharCompare {
+  int op;
+  const CharLiteral &lit;
+  struct Key16 {
+    unsigned long long first, second;   // the literal's first / second eight bytes, big-endian, zero-padded
+  };
+  __device__ __forceinline__ bool fits16() const { return lit.length <= 16; }
+  __device__ __forceinline__ Key16 key16() const {
+    Key16 key{0, 0};
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      key.first |= static_cast<unsigned long long>(i < lit.length ? lit.bytes[i] : 0) << (8 * (7 - i));
+      key.second |= static_cast<unsigned long long>(8 + i < lit.length ? lit.bytes[8 + i] : 0) << (8 * (7 - i));
+    }
+    return key;
+  }
+  // strcmp on zero-padded 16-byte strings = an unsigned compare of their bytes read as one big-endian number
+  __device__ __forceinline__ bool match16(const Key16 &key, unsigned long long x_first, unsigned long long x_second) const {
+    const int res = x_first != key.first ? (x_first < key.first ? -1 : 1) : (x_second != key.second ? (x_second < key.second ? -1 : 1) : 0);
+    return compare_op<int>(res, op, 0);
+  }
+  __device__ __forceinline__ bool match(const unsigned char *v, int width) const {
+    int res = 0;
+    const int longest = width > lit.length ? width : lit.length;
+    for (int i = 0; i < longest; ++i) {
+      const unsigned char a = i < width ? v[i] : 0;
+      const unsigned char b = i < lit.length ? lit.bytes[i] : 0;
+      if (a != b) {
+        res = a < b ? -1 : 1;
+        break;
+      }
+      if (a == 0) break;
+    }
+    return compare_op<int>(res, op, 0);
+  }
+};
+// One tile (rows [row0, row0 + tile_rows) of a stripe) of a test of CHAR texts (Cmp: CharCompare, CharInCompare); lane 0 of
+// every wave adds its words' bits to count.
+template <typename Cmp>
+__device__ __forceinline__ void select_char_tile(const unsigned char *__restrict__ col, int width, int64_t n, const Cmp &cmp,
                                                  const uint64_t *__restrict__ filter, uint64_t *__restrict__ out, int64_t row0,
                                                  int tile_rows, unsigned char *s_tile, unsigned long long &count) {
   const int lane = lane_id();
   const int wave = threadIdx.x >> 6;
   const int rows = static_cast<int>(n - row0 < tile_rows ? n - row0 : tile_rows);
-  if (width <= 16 && lit.length <= 16 && (reinterpret_cast<uintptr_t>(col) & 3) == 0) {
+  if (width <= 16 && cmp.fits16() && (reinterpret_cast<uintptr_t>(col) & 3) == 0) {
     // short fields (c_mktsegment CHAR(10), l_shipmode CHAR(10), flags): no workgroup-wide staging, no barrier — wave by wave
     // (below); a row is compared in registers, 16 bytes from its first byte on.  Through a tile in LDS a workgroup pays load ->
     // store -> barrier -> a byte-at-a-time walk per tile: 0.236 ms per 25 M CHAR(10) rows.
@@ -1141,12 +1184,7 @@ __device__ __forceinline__ void select_char_tile(const unsigned char *__restrict
     const int strip_words = 16 * width + 1;   // (+ 1: a row's fifth word may lie behind the last row)
     const unsigned long long width_mask_lo = width >= 8 ? ~0ull : ((1ull << (8 * width)) - 1ull);
     const unsigned long long width_mask_hi = width >= 16 ? ~0ull : (width > 8 ? ((1ull << (8 * (width - 8))) - 1ull) : 0ull);
-    unsigned long long lit_first = 0, lit_second = 0;   // the literal's first / second eight bytes, big-endian, zero-padded
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      lit_first |= static_cast<unsigned long long>(i < lit.length ? lit.bytes[i] : 0) << (8 * (7 - i));
-      lit_second |= static_cast<unsigned long long>(8 + i < lit.length ? lit.bytes[8 + i] : 0) << (8 * (7 - i));
-    }
+    const typename Cmp::Key16 key = cmp.key16();
     // words a row can touch from its first byte's word on: 2 (width <= 4), 3 (<= 8), 5 (<= 16) — also the rounds of 64 lanes
     // that load a bitmap word's rows
     auto rows_of_wave = [&](auto kw_tag) {
@@ -1200,9 +1238,8 @@ __device__ __forceinline__ void select_char_tile(const unsigned char *__restrict
           } else {                          // width <= 4: inside the second
             lo = q0 >> shift[u];
           }
-          // strcmp on zero-padded 16-byte strings = an unsigned compare of their bytes read as one big-endian number: bytes from
-          // the field's width on and everything behind its first NUL are cleared (the literal's were, by the host), then two
-          // 64-bit compares.  (A byte-at-a-time walk with a "decided" flag was ~130 instructions per row: the kernel took
+          // The text as one big-endian number (Cmp::match16): bytes from the field's width on and everything behind its
+          // first NUL are cleared (the literal's were, by the host), then two 64-bit compares.  (A byte-at-a-time walk with a "decided" flag was ~130 instructions per row: the kernel took
           // 0.11 ms per 25 M rows whatever the width — CHAR(1) included.)
           const unsigned long long a_lo = lo & width_mask_lo, a_hi = hi & width_mask_hi;
           const unsigned long long keep_lo = up_to_first_zero_byte(a_lo);
@@ -1210,8 +1247,7 @@ __device__ __forceinline__ void select_char_tile(const unsigned char *__restrict
           unsigned long long s_hi = 0;
           if constexpr (KW == 5) s_hi = keep_lo == ~0ull ? (a_hi & up_to_first_zero_byte(a_hi)) : 0ull;
           const unsigned long long x_first = __builtin_bswap64(s_lo), x_second = __builtin_bswap64(s_hi);
-          const int res = x_first != lit_first ? (x_first < lit_first ? -1 : 1) : (x_second != lit_second ? (x_second < lit_second ? -1 : 1) : 0);
-          const bool pred = r < rows && compare_op<int>(res, op, 0);
+          const bool pred = r < rows && cmp.match16(key, x_first, x_second);
           uint64_t word = msb_first(__ballot(pred));
           const int64_t word_index = (row0 >> 6) + w;
           if (filter != nullptr) word &= filter[word_index];
@@ -1243,23 +1279,7 @@ __device__ __forceinline__ void select_char_tile(const unsigned char *__restrict
   for (int w = wave; w * 64 < rows; w += kWavesPerBlock) {
     const int r = w * 64 + lane;
     bool pred = false;
-    if (r < rows) {
-      const unsigned char *v = s_tile + r * width;
-      int res = 0;
-      {
-        const int longest = width > lit.length ? width : lit.length;
-        for (int i = 0; i < longest; ++i) {
-          const unsigned char a = i < width ? v[i] : 0;
-          const unsigned char b = i < lit.length ? lit.bytes[i] : 0;
-          if (a != b) {
-            res = a < b ? -1 : 1;
-            break;
-          }
-          if (a == 0) break;
-        }
-      }
-      pred = compare_op<int>(res, op, 0);
-    }
+    if (r < rows) pred = cmp.match(s_tile + r * width, width);
     uint64_t word = msb_first(__ballot(pred));
     const int64_t word_index = (row0 >> 6) + w;
     if (filter != nullptr) word &= filter[word_index];
@@ -1279,7 +1299,7 @@ __global__ __launch_bounds__(kBlock) void select_char_kernel(const unsigned char
   const int64_t num_tiles = (n + tile_rows - 1) / tile_rows;
   unsigned long long count = 0;
   for (int64_t tile = blockIdx.x; tile < num_tiles; tile += gridDim.x) {
-    select_char_tile(col, width, n, op, lit, filter, out, tile * tile_rows, tile_rows, s_tile, count);
+    select_char_tile(col, width, n, CharCompare{op, lit}, filter, out, tile * tile_rows, tile_rows, s_tile, count);
   }
   if (out_count != nullptr) {
     __shared__ unsigned long long block_count;
@@ -1309,7 +1329,170 @@ __global__ __launch_bounds__(kBlock) void select_char_runs_kernel(const long lon
       count = 0;
       counted_block = at.block;
     }
-    select_char_tile(run_in<unsigned char>(runs, at.block), width, run_rows(runs, at.block), op, lit, run_filter(runs, at.block),
+    select_char_tile(run_in<unsigned char>(runs, at.block), width, run_rows(runs, at.block), CharCompare{op, lit}, run_filter(runs, at.block),
+                     run_out<uint64_t>(runs, at.block), static_cast<int64_t>(at.tile_in_block) * tile_rows, tile_rows, s_tile, count);
+  }
+  if (out_counts != nullptr && counted_block >= 0 && lane == 0 && count != 0) atomicAdd(&out_counts[counted_block], count);
+}
+
+// ---------------------------------------------------------------------------
+// IN lists (qsx_select_in, qsx_select_in_char): out[i] = ((col[i] == some literal) XOR negate) [AND filter[i]] in ONE pass
+// over the stripe, whatever the number of literals.  The reference has no IN node: InValueList::concretize
+// (query_optimizer/expressions/InValueList.cpp:40-65) makes a disjunction of kEqual comparisons, which
+// DisjunctionPredicate::getAllMatches (expressions/predicate/DisjunctionPredicate.cpp:109-157) evaluates as one scan per
+// literal and a union; NOT IN is NegationPredicate::getAllMatches (NegationPredicate.cpp:70-90) over it.
+// A numeric list is a predicate of the packed scan above (select_packed_group: 16 bytes per lane and load, the lanes of a
+// bitmap word merge their masks) with the literals as wave-uniform kernel arguments; a CHAR list is a test of
+// select_char_tile, which loads a row's bytes once and compares them with every literal.
+// ---------------------------------------------------------------------------
+template <typename T>
+struct InListPred {
+  T lits[QSX_MAX_IN_LIST];   // padded by the host to a multiple of four with copies of the first literal
+  int count;                 // multiple of 4
+  bool negate;
+  // Equality is the type's own ==: NaN is in no list, -0.0 equals 0.0 (LiteralComparators-inl.hpp:330-370 with EqualFunctor).
+  __device__ __forceinline__ bool operator()(T v) const {
+    bool any = false;
+#pragma unroll
+    for (int g = 0; g < QSX_MAX_IN_LIST; g += 4) {   // constant indices: the literals stay in scalar registers
+      if (g >= count) break;                         // wave-uniform
+      any = any || v == lits[g] || v == lits[g + 1] || v == lits[g + 2] || v == lits[g + 3];
+    }
+    return any != negate;
+  }
+};
+
+// A stripe whose start the packed kernel may not take (aligned16): a row per lane, the wave layout of select_cmp_kernel.
+template <typename T, int R>
+__global__ __launch_bounds__(kBlock) void select_in_rows_kernel(const T *__restrict__ col, int64_t n, InListPred<T> pred,
+                                                               const uint64_t *__restrict__ filter, uint64_t *__restrict__ out,
+                                                               unsigned long long *__restrict__ out_count) {
+  const int lane = lane_id();
+  const int64_t num_words = (n + 63) >> 6;
+  const int64_t wave = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
+  const int64_t num_waves = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
+  unsigned long long count = 0;
+  for (int64_t w0 = wave * R; w0 < num_words; w0 += num_waves * R) {
+    T v[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int64_t row = ((w0 + r) << 6) + lane;
+      v[r] = load_global_nt(&col[row < n ? row : n - 1]);   // clamped; rows past n are masked out of the ballot
+    }
+    uint64_t mine = 0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int64_t row = ((w0 + r) << 6) + lane;
+      uint64_t word = msb_first(__ballot(row < n && pred(v[r])));
+      if (filter != nullptr && w0 + r < num_words) word &= filter[w0 + r];
+      count += __popcll(word);
+      if (lane == r) mine = word;
+    }
+    if (lane < R && w0 + lane < num_words) out[w0 + lane] = mine;
+  }
+  if (out_count != nullptr) {
+    __shared__ unsigned long long block_count;
+    if (threadIdx.x == 0) block_count = 0;
+    __syncthreads();
+    if (lane == 0 && count != 0) atomicAdd(&block_count, count);
+    __syncthreads();
+    if (threadIdx.x == 0 && block_count != 0) atomicAdd(out_count, block_count);
+  }
+}
+
+// A CHAR list in device memory (staged alone, or behind the run table): read with wave-uniform indices.  Only the literals
+// that can equal a field of the stripe's width are kept (no longer than it), so on fields of width <= 16 every literal lies
+// in `first` / `second`.  The host pads the list to a multiple of four with copies of its first literal: the register path
+// fetches four literals at a time and compares without a branch.
+struct CharInList {
+  long long count, negate;                                              // count: a multiple of 4 (0: no literal can match)
+  long long wide;                                                       // some literal is longer than 8 bytes: `second` takes part
+  long long direct;                                                     // the host sized tiles and LDS for the register path (below)
+  unsigned long long first[QSX_MAX_IN_LIST], second[QSX_MAX_IN_LIST];   // bytes 0-7 / 8-15, big-endian, zero-padded
+  long long length[QSX_MAX_IN_LIST];                                    // bytes before the first NUL
+  unsigned char bytes[QSX_MAX_IN_LIST][QSX_MAX_CHAR_LITERAL];
+};
+static_assert(sizeof(CharInList) % 8 == 0, "lies in a table of 64-bit words");
+struct CharInCompare {
+  const CharInList *__restrict__ list;
+  struct Key16 {};
+  // The register path only where the host chose it for the whole launch (fields of width <= 16, EVERY stripe of the run on a
+  // 4-byte boundary): its tile size and its LDS strips are the host's to provide, so host and kernel must not decide apart.
+  __device__ __forceinline__ bool fits16() const { return list->direct != 0; }
+  __device__ __forceinline__ Key16 key16() const { return Key16{}; }
+  // strcmpHelper equality (AsciiStringComparators.hpp:218-251) of zero-padded texts: both 64-bit halves are the same.
+  // (`|` and `&`, not `||` and `&&`: one literal at a time behind a branch waited for a scalar load per comparison —
+  // 0.62 ms per 100 M CHAR(2) rows against 7 literals.)
+  __device__ __forceinline__ bool match16(const Key16 &, unsigned long long x_first, unsigned long long x_second) const {
+    bool any = false;
+    const int count = static_cast<int>(list->count);
+    if (list->wide != 0) {
+      for (int i = 0; i < count; i += 4) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) any |= (x_first == list->first[i + j]) & (x_second == list->second[i + j]);
+      }
+    } else {   // no literal reaches the second half: the text must end inside the first
+      for (int i = 0; i < count; i += 4) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) any |= x_first == list->first[i + j];
+      }
+      any &= x_second == 0ull;
+    }
+    return any != (list->negate != 0);
+  }
+  __device__ __forceinline__ bool match(const unsigned char *v, int width) const {
+    bool any = false;
+    const int count = static_cast<int>(list->count);
+    for (int i = 0; i < count && !any; ++i) {
+      const int len = static_cast<int>(list->length[i]);          // <= width
+      bool same = len == width || v[len] == 0;                    // the text ends where the literal does
+      for (int j = 0; j < len && same; ++j) same = v[j] == list->bytes[i][j];
+      any = same;
+    }
+    return any != (list->negate != 0);
+  }
+};
+
+__global__ __launch_bounds__(kBlock) void select_in_char_kernel(const unsigned char *__restrict__ col, int width, int64_t n,
+                                                               const CharInList *__restrict__ list, const uint64_t *__restrict__ filter,
+                                                               uint64_t *__restrict__ out, unsigned long long *__restrict__ out_count,
+                                                               int tile_rows) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_tile[];
+  const int lane = lane_id();
+  const int64_t num_tiles = (n + tile_rows - 1) / tile_rows;
+  unsigned long long count = 0;
+  for (int64_t tile = blockIdx.x; tile < num_tiles; tile += gridDim.x) {
+    select_char_tile(col, width, n, CharInCompare{list}, filter, out, tile * tile_rows, tile_rows, s_tile, count);
+  }
+  if (out_count != nullptr) {
+    __shared__ unsigned long long block_count;
+    if (threadIdx.x == 0) block_count = 0;
+    __syncthreads();
+    if (lane == 0 && count != 0) atomicAdd(&block_count, count);
+    __syncthreads();
+    if (threadIdx.x == 0 && block_count != 0) atomicAdd(out_count, block_count);
+  }
+}
+
+// Over a run of blocks (as select_char_runs_kernel); the list lies behind the run table at word `extra`.
+__global__ __launch_bounds__(kBlock) void select_in_char_runs_kernel(const long long *__restrict__ runs, int width, long long extra,
+                                                                    unsigned long long *__restrict__ out_counts, int tile_rows) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_tile[];
+  const int lane = lane_id();
+  const CharInList *list = reinterpret_cast<const CharInList *>(runs + extra);
+  const long long num_tiles = runs[2];
+  const int first = static_cast<int>(num_tiles * blockIdx.x / gridDim.x);
+  const int end = static_cast<int>(num_tiles * (blockIdx.x + 1) / gridDim.x);
+  unsigned long long count = 0;
+  int counted_block = -1;
+  for (int tile = first; tile < end; ++tile) {
+    const RunTile at = run_locate(runs, tile);
+    if (at.block != counted_block) {
+      if (out_counts != nullptr && counted_block >= 0 && lane == 0 && count != 0) atomicAdd(&out_counts[counted_block], count);
+      count = 0;
+      counted_block = at.block;
+    }
+    select_char_tile(run_in<unsigned char>(runs, at.block), width, run_rows(runs, at.block), CharInCompare{list}, run_filter(runs, at.block),
                      run_out<uint64_t>(runs, at.block), static_cast<int64_t>(at.tile_in_block) * tile_rows, tile_rows, s_tile, count);
   }
   if (out_counts != nullptr && counted_block >= 0 && lane == 0 && count != 0) atomicAdd(&out_counts[counted_block], count);
@@ -1455,6 +1638,75 @@ static int sorted_runs(int64_t num_blocks, const int64_t *block_rows, const void
   return QSX_OK;
 }
 
+// ---- IN lists: host side ---------------------------------------------------------------------------------------------------
+template <typename T>
+static InListPred<T> in_list_pred(const void *literals, int num_literals, int negate) {
+  InListPred<T> pred{};
+  std::memcpy(pred.lits, literals, sizeof(T) * static_cast<size_t>(num_literals));
+  pred.count = (num_literals + 3) / 4 * 4;
+  for (int i = num_literals; i < pred.count; ++i) pred.lits[i] = pred.lits[0];   // duplicates change nothing
+  pred.negate = negate != 0;
+  return pred;
+}
+template <typename T>
+static int launch_select_in(const void *col, int64_t n, const void *literals, int num_literals, int negate, const uint64_t *filter,
+                            uint64_t *out, int64_t *out_count, hipStream_t stream) {
+  const InListPred<T> pred = in_list_pred<T>(literals, num_literals, negate);
+  if (aligned16(col)) return launch_select_packed<T>(col, n, pred, filter, out, out_count, stream);
+  constexpr int R = sizeof(T) == 4 ? 8 : 4;
+  const int grid = grid_for((n + 63) >> 6, kWavesPerBlock * R);
+  hipLaunchKernelGGL((select_in_rows_kernel<T, R>), dim3(grid), dim3(kBlock), 0, stream, static_cast<const T *>(col), n, pred, filter, out,
+                     reinterpret_cast<unsigned long long *>(out_count));
+  QSX_CHECK_LAUNCH();
+  return QSX_OK;
+}
+template <typename T>
+static int launch_select_in_runs(const long long *runs_dev, long long tiles, const void *literals, int num_literals, int negate,
+                                 int64_t *out_counts, hipStream_t stream) {
+  constexpr int R = 4;
+  const int grid = grid_for(tiles, kWavesPerBlock);
+  hipLaunchKernelGGL((select_packed_runs_kernel<T, InListPred<T>, R>), dim3(grid), dim3(kBlock), 0, stream, runs_dev,
+                     in_list_pred<T>(literals, num_literals, negate), reinterpret_cast<unsigned long long *>(out_counts), 0ll);
+  QSX_CHECK_LAUNCH();
+  return QSX_OK;
+}
+// The list as the CHAR kernels read it, or QSX_ERR_UNSUPPORTED for a literal of more than QSX_MAX_CHAR_LITERAL bytes.
+static int char_in_list(int width, const void *literals, const int32_t *literal_lengths, int num_literals, int negate, CharInList *list) {
+  std::memset(list, 0, sizeof(CharInList));
+  list->negate = negate;
+  for (int k = 0; k < num_literals; ++k) {
+    if (literal_lengths[k] < 0) return QSX_ERR_INVALID_ARGUMENT;
+    if (literal_lengths[k] > QSX_MAX_CHAR_LITERAL) return QSX_ERR_UNSUPPORTED;
+  }
+  for (int k = 0; k < num_literals; ++k) {
+    const unsigned char *text = static_cast<const unsigned char *>(literals) + static_cast<size_t>(k) * QSX_MAX_CHAR_LITERAL;
+    int len = 0;
+    while (len < literal_lengths[k] && text[len] != 0) ++len;   // a NUL ends it
+    if (len > width) continue;                                  // equals no field of this width
+    const long long at = list->count++;
+    list->length[at] = len;
+    if (len > 8) list->wide = 1;
+    for (int i = 0; i < len; ++i) {
+      list->bytes[at][i] = text[i];
+      if (i < 8) list->first[at] |= static_cast<unsigned long long>(text[i]) << (8 * (7 - i));
+      else if (i < 16) list->second[at] |= static_cast<unsigned long long>(text[i]) << (8 * (15 - i));
+    }
+  }
+  for (; list->count % 4 != 0; ++list->count) {   // a multiple of four, by copies of the first literal: duplicates change nothing
+    list->first[list->count] = list->first[0];
+    list->second[list->count] = list->second[0];
+    list->length[list->count] = list->length[0];
+    std::memcpy(list->bytes[list->count], list->bytes[0], QSX_MAX_CHAR_LITERAL);
+  }
+  return QSX_OK;
+}
+static int char_tile_rows(int width) {   // as qsx_select_cmp_char: a multiple of 64 (whole bitmap words), at most 48 KiB of LDS
+  int tile_rows = (48 * 1024 / width) / 64 * 64;
+  if (tile_rows > 1024) tile_rows = 1024;
+  if (tile_rows < 64) tile_rows = 64;
+  return tile_rows;
+}
+
 extern "C" {
 
 int qsx_select_cmp_char(const void *col_dev, int width, int64_t n, int op, const void *literal, int literal_length,
@@ -1524,7 +1776,10 @@ int qsx_select_cmp_char_blocks(int width, int64_t num_blocks, const int64_t *blo
   if (rc != QSX_OK) return rc;
   const long long *runs_dev = table.dev();
   const int grid = tile_grid(tiles);
-  const size_t lds = direct ? kCharDirectLds : (static_cast<size_t>(tile_rows) * width + 15) / 16 * 16;
+  size_t lds = direct ? kCharDirectLds : (static_cast<size_t>(tile_rows) * width + 15) / 16 * 16;
+  // (select_char_tile takes the register path block by block: in a run whose stripes differ in alignment the aligned blocks
+  // still use its per-wave strips, which must lie inside the allocation)
+  if (!direct && width <= 16 && lit.length <= 16 && lds < kCharDirectLds) lds = kCharDirectLds;
   hipLaunchKernelGGL(select_char_runs_kernel, dim3(grid), dim3(kBlock), lds, s, runs_dev, width, op, lit,
                      reinterpret_cast<unsigned long long *>(out_counts_dev), tile_rows);
   QSX_CHECK_LAUNCH();
@@ -1594,6 +1849,132 @@ int qsx_select_cmp_blocks(int type, int64_t num_blocks, const int64_t *block_row
     case QSX_DATE: return dispatch_select_runs<DateValue>(op, runs_dev, tiles, literal, out_counts_dev, s);
     default: return QSX_ERR_UNSUPPORTED;
   }
+}
+
+int qsx_select_in(int type, const void *col_dev, int64_t n, const void *literals, int num_literals, int negate,
+                  const uint64_t *filter_dev, uint64_t *out_bitmap_dev, int64_t *out_count_dev, qsx_stream_t stream) {
+  QSX_REQUIRE_DEVICE();
+  if (n < 0 || literals == nullptr || num_literals < 1 || num_literals > QSX_MAX_IN_LIST || (negate != 0 && negate != 1) ||
+      (n > 0 && (col_dev == nullptr || out_bitmap_dev == nullptr))) {
+    return QSX_ERR_INVALID_ARGUMENT;
+  }
+  if (type_width(type) == 0) return QSX_ERR_UNSUPPORTED;
+  hipStream_t s = as_stream(stream);
+  if (out_count_dev != nullptr) QSX_HIP_TRY(hipMemsetAsync(out_count_dev, 0, sizeof(int64_t), s));
+  if (n == 0) return QSX_OK;
+  switch (type) {
+    case QSX_INT: return launch_select_in<int32_t>(col_dev, n, literals, num_literals, negate, filter_dev, out_bitmap_dev, out_count_dev, s);
+    case QSX_LONG: return launch_select_in<int64_t>(col_dev, n, literals, num_literals, negate, filter_dev, out_bitmap_dev, out_count_dev, s);
+    case QSX_FLOAT: return launch_select_in<float>(col_dev, n, literals, num_literals, negate, filter_dev, out_bitmap_dev, out_count_dev, s);
+    case QSX_DOUBLE: return launch_select_in<double>(col_dev, n, literals, num_literals, negate, filter_dev, out_bitmap_dev, out_count_dev, s);
+    default: return launch_select_in<DateValue>(col_dev, n, literals, num_literals, negate, filter_dev, out_bitmap_dev, out_count_dev, s);
+  }
+}
+
+int qsx_select_in_blocks(int type, int64_t num_blocks, const int64_t *block_rows, const void *const *block_cols, const void *literals,
+                         int num_literals, int negate, const uint64_t *const *block_filters, uint64_t *const *block_out_bitmaps,
+                         int64_t *out_counts_dev, qsx_stream_t stream) {
+  QSX_REQUIRE_DEVICE();
+  if (num_blocks < 0 || literals == nullptr || num_literals < 1 || num_literals > QSX_MAX_IN_LIST || (negate != 0 && negate != 1) ||
+      (num_blocks > 0 && (block_rows == nullptr || block_cols == nullptr || block_out_bitmaps == nullptr))) {
+    return QSX_ERR_INVALID_ARGUMENT;
+  }
+  const int width = type_width(type);
+  if (width == 0) return QSX_ERR_UNSUPPORTED;
+  if (!run_blocks_ok(num_blocks, block_rows, block_cols, reinterpret_cast<const void *const *>(block_out_bitmaps))) return QSX_ERR_INVALID_ARGUMENT;
+  if (num_blocks == 0) return QSX_OK;
+  bool aligned = true;
+  for (int64_t b = 0; b < num_blocks; ++b) aligned = aligned && aligned16(block_cols[b]);
+  if (!aligned) {   // (as qsx_select_cmp_blocks: the row-per-lane kernel, block by block)
+    for (int64_t b = 0; b < num_blocks; ++b) {
+      const int rc = qsx_select_in(type, block_cols[b], block_rows[b], literals, num_literals, negate, block_filters != nullptr ? block_filters[b] : nullptr,
+                                   block_out_bitmaps[b], out_counts_dev != nullptr ? out_counts_dev + b : nullptr, stream);
+      if (rc != QSX_OK) return rc;
+    }
+    return QSX_OK;
+  }
+  hipStream_t s = as_stream(stream);
+  if (out_counts_dev != nullptr) QSX_HIP_TRY(hipMemsetAsync(out_counts_dev, 0, sizeof(int64_t) * static_cast<size_t>(num_blocks), s));
+  constexpr int kLoadsPerTile = 4;                                   // R of select_packed_runs_kernel
+  const long long tile_rows = static_cast<long long>(kWave) * (16 / width) * kLoadsPerTile;
+  RunTable table;
+  const long long tiles = table.build(tile_rows, num_blocks, block_rows, block_cols, reinterpret_cast<const void *const *>(block_filters),
+                                      reinterpret_cast<void *const *>(block_out_bitmaps), nullptr);
+  if (tiles < 0) return QSX_ERR_INVALID_ARGUMENT;
+  if (tiles == 0) return QSX_OK;
+  const int rc = table.upload(s);
+  if (rc != QSX_OK) return rc;
+  switch (type) {
+    case QSX_INT: return launch_select_in_runs<int32_t>(table.dev(), tiles, literals, num_literals, negate, out_counts_dev, s);
+    case QSX_LONG: return launch_select_in_runs<int64_t>(table.dev(), tiles, literals, num_literals, negate, out_counts_dev, s);
+    case QSX_FLOAT: return launch_select_in_runs<float>(table.dev(), tiles, literals, num_literals, negate, out_counts_dev, s);
+    case QSX_DOUBLE: return launch_select_in_runs<double>(table.dev(), tiles, literals, num_literals, negate, out_counts_dev, s);
+    default: return launch_select_in_runs<DateValue>(table.dev(), tiles, literals, num_literals, negate, out_counts_dev, s);
+  }
+}
+
+int qsx_select_in_char(const void *col_dev, int width, int64_t n, const void *literals, const int32_t *literal_lengths, int num_literals,
+                       int negate, const uint64_t *filter_dev, uint64_t *out_bitmap_dev, int64_t *out_count_dev, qsx_stream_t stream) {
+  QSX_REQUIRE_DEVICE();
+  if (n < 0 || width < 1 || width > 255 || literals == nullptr || literal_lengths == nullptr || num_literals < 1 ||
+      num_literals > QSX_MAX_IN_LIST || (negate != 0 && negate != 1) || (n > 0 && (col_dev == nullptr || out_bitmap_dev == nullptr))) {
+    return QSX_ERR_INVALID_ARGUMENT;
+  }
+  CharInList list;
+  int rc = char_in_list(width, literals, literal_lengths, num_literals, negate, &list);
+  if (rc != QSX_OK) return rc;
+  hipStream_t s = as_stream(stream);
+  if (out_count_dev != nullptr) QSX_HIP_TRY(hipMemsetAsync(out_count_dev, 0, sizeof(int64_t), s));
+  if (n == 0) return QSX_OK;
+  // short fields in a 4-byte aligned stripe are read straight from it (select_char_tile): 16 bitmap words per wave and tile
+  const bool direct = width <= 16 && (reinterpret_cast<uintptr_t>(col_dev) & 3) == 0;
+  list.direct = direct ? 1 : 0;
+  const CharInList *list_dev = nullptr;
+  rc = staged_table(s, &list, sizeof(list), &list_dev);
+  if (rc != QSX_OK) return rc;
+  const int tile_rows = direct ? 4096 : char_tile_rows(width);
+  const int64_t tiles = (n + tile_rows - 1) / tile_rows;
+  const size_t lds = direct ? kCharDirectLds : (static_cast<size_t>(tile_rows) * width + 15) / 16 * 16;
+  hipLaunchKernelGGL(select_in_char_kernel, dim3(tile_grid(tiles)), dim3(kBlock), lds, s, static_cast<const unsigned char *>(col_dev), width, n,
+                     list_dev, filter_dev, out_bitmap_dev, reinterpret_cast<unsigned long long *>(out_count_dev), tile_rows);
+  QSX_CHECK_LAUNCH();
+  return QSX_OK;
+}
+
+int qsx_select_in_char_blocks(int width, int64_t num_blocks, const int64_t *block_rows, const void *const *block_cols, const void *literals,
+                              const int32_t *literal_lengths, int num_literals, int negate, const uint64_t *const *block_filters,
+                              uint64_t *const *block_out_bitmaps, int64_t *out_counts_dev, qsx_stream_t stream) {
+  QSX_REQUIRE_DEVICE();
+  if (num_blocks < 0 || width < 1 || width > 255 || literals == nullptr || literal_lengths == nullptr || num_literals < 1 ||
+      num_literals > QSX_MAX_IN_LIST || (negate != 0 && negate != 1) ||
+      (num_blocks > 0 && (block_rows == nullptr || block_cols == nullptr || block_out_bitmaps == nullptr))) {
+    return QSX_ERR_INVALID_ARGUMENT;
+  }
+  CharInList list;
+  int rc = char_in_list(width, literals, literal_lengths, num_literals, negate, &list);
+  if (rc != QSX_OK) return rc;
+  if (num_blocks == 0) return QSX_OK;
+  if (!run_blocks_ok(num_blocks, block_rows, block_cols, reinterpret_cast<const void *const *>(block_out_bitmaps))) return QSX_ERR_INVALID_ARGUMENT;
+  hipStream_t s = as_stream(stream);
+  if (out_counts_dev != nullptr) QSX_HIP_TRY(hipMemsetAsync(out_counts_dev, 0, sizeof(int64_t) * static_cast<size_t>(num_blocks), s));
+  // one decision for the run: a single stripe off a 4-byte boundary sends every block through the LDS tile
+  bool direct = width <= 16;
+  for (int64_t b = 0; b < num_blocks && direct; ++b) direct = block_rows[b] == 0 || (reinterpret_cast<uintptr_t>(block_cols[b]) & 3) == 0;
+  list.direct = direct ? 1 : 0;
+  const int tile_rows = direct ? 4096 : char_tile_rows(width);
+  RunTable table;
+  const long long tiles = table.build(tile_rows, num_blocks, block_rows, block_cols, reinterpret_cast<const void *const *>(block_filters),
+                                      reinterpret_cast<void *const *>(block_out_bitmaps), nullptr);
+  if (tiles < 0) return QSX_ERR_INVALID_ARGUMENT;
+  if (tiles == 0) return QSX_OK;
+  const long long extra = table.append(sizeof(CharInList) / 8, reinterpret_cast<const long long *>(&list));
+  rc = table.upload(s);
+  if (rc != QSX_OK) return rc;
+  const size_t lds = direct ? kCharDirectLds : (static_cast<size_t>(tile_rows) * width + 15) / 16 * 16;
+  hipLaunchKernelGGL(select_in_char_runs_kernel, dim3(tile_grid(tiles)), dim3(kBlock), lds, s, table.dev(), width, extra,
+                     reinterpret_cast<unsigned long long *>(out_counts_dev), tile_rows);
+  QSX_CHECK_LAUNCH();
+  return QSX_OK;
 }
 
 int qsx_select_cmp_sorted(int type, const void *col_dev, int64_t n, int op, const void *literal, const uint64_t *filter_dev,

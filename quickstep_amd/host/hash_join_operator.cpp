@@ -45,6 +45,12 @@ bool HashJoinOperator::getAllWorkOrders(WorkOrdersContainer *container, QueryCon
   if (is_selection_on_build_.empty()) is_selection_on_build_.assign(selection.size(), false);
   InsertDestination *dest = query_context->getInsertDestination(output_destination_index_);
   CheckRepartition("HashJoinOperator", has_repartition_, dest);
+  const Predicate *residual = query_context->getPredicate(residual_predicate_index_);
+  if (residual != nullptr && residual->tree != nullptr) {
+    // the residual is evaluated term by term on gathered pairs (qsx_select_cmp_columns): there are no leaf bitmaps to combine
+    throw ExecutionError("HashJoinOperator: a residual predicate with a tree (OR / NOT / IN); only a conjunction of comparisons",
+                         QSX_ERR_UNSUPPORTED);
+  }
   std::lock_guard<std::mutex> lock(mutex_);
   if (!started_) {
     // the build operator is a blocking dependency: it has published its key attributes by now

@@ -27,6 +27,335 @@ void SelectCharTerm(const ComparisonPredicate &term, const void *stripe, int wid
               "qsx_select_cmp_char");
 }
 
+// ---------------------------------------------------------------------------
+// Predicate trees: builders, the leaves of a tree and its postfix program
+// ---------------------------------------------------------------------------
+PredicateNodePtr Predicate::Compare(const ComparisonPredicate &term) {
+  auto n = std::make_shared<PredicateNode>();
+  n->kind = PredicateNode::kComparison;
+  n->comparison = term;
+  return n;
+}
+PredicateNodePtr Predicate::In(attribute_id operand, std::vector<TypedLiteral> literals) {
+  auto n = std::make_shared<PredicateNode>();
+  n->kind = PredicateNode::kInList;
+  n->comparison.attribute = operand;
+  n->comparison.comparison = ComparisonID::kEqual;
+  n->in_literals = std::move(literals);
+  return n;
+}
+static PredicateNodePtr NodeOver(PredicateNode::Kind kind, std::vector<PredicateNodePtr> children) {
+  auto n = std::make_shared<PredicateNode>();
+  n->kind = kind;
+  n->children = std::move(children);
+  return n;
+}
+PredicateNodePtr Predicate::And(std::vector<PredicateNodePtr> children) { return NodeOver(PredicateNode::kConjunction, std::move(children)); }
+PredicateNodePtr Predicate::Or(std::vector<PredicateNodePtr> children) { return NodeOver(PredicateNode::kDisjunction, std::move(children)); }
+PredicateNodePtr Predicate::Not(PredicateNodePtr child) { return NodeOver(PredicateNode::kNegation, {std::move(child)}); }
+
+namespace {
+std::atomic<std::int64_t> tree_block_evaluations{0}, tree_run_evaluations{0};
+
+// The literals of an IN leaf as the C ABI takes them (qsx_select_in / qsx_select_in_char): at most QSX_MAX_IN_LIST of them.
+struct InListLiterals {
+  std::vector<unsigned char> values;   // numeric / DATE: the operand type's bytes, one literal behind the other
+  std::vector<char> slots;             // CHAR: QSX_MAX_CHAR_LITERAL bytes each
+  std::vector<std::int32_t> lengths;
+  int count = 0;
+};
+InListLiterals MakeInList(const Type &t, const std::vector<TypedLiteral> &literals, std::size_t begin, std::size_t end) {
+  InListLiterals out;
+  out.count = static_cast<int>(end - begin);
+  for (std::size_t k = begin; k < end; ++k) {
+    const TypedLiteral &l = literals[k];
+    if (l.type != t.id) throw ExecutionError("IN list: a literal whose type differs from the operand's", QSX_ERR_UNSUPPORTED);
+    if (t.id == kChar) {
+      if (l.text.size() > QSX_MAX_CHAR_LITERAL) throw ExecutionError("IN list: a literal longer than QSX_MAX_CHAR_LITERAL bytes", QSX_ERR_UNSUPPORTED);
+      out.slots.resize(out.slots.size() + QSX_MAX_CHAR_LITERAL, 0);
+      std::memcpy(out.slots.data() + out.slots.size() - QSX_MAX_CHAR_LITERAL, l.text.data(), l.text.size());
+      out.lengths.push_back(static_cast<std::int32_t>(l.text.size()));
+    } else {
+      const unsigned char *bytes = reinterpret_cast<const unsigned char *>(&l.v);
+      out.values.insert(out.values.end(), bytes, bytes + t.width);
+    }
+  }
+  return out;
+}
+
+// A leaf of a compiled tree: a term (a comparison, or an IN list when `in` is set) or an attribute's null bitmap.
+struct TreeLeaf {
+  ComparisonPredicate term;
+  std::shared_ptr<InListLiterals> in;
+  const std::vector<TypedLiteral> *in_source = nullptr;   // the literals [in_begin, in_end) of it (to recognise the same list twice)
+  std::size_t in_begin = 0, in_end = 0;
+  attribute_id null_of = kInvalidAttributeID;              // != invalid: the null bitmap of this attribute
+};
+struct TreeProgram {
+  std::vector<TreeLeaf> leaves;
+  std::vector<std::int32_t> program;
+};
+bool SameLiteral(const TypedLiteral &a, const TypedLiteral &b) { return a.type == b.type && a.v.i64 == b.v.i64 && a.text == b.text; }
+
+// has_nulls(a): some block at hand holds a null bitmap for a.  expand_in(a): an IN list over a is written as equalities
+// (a truncated attribute without a dictionary: TransformPredicateOnCompressedAttribute rewrites each on the codes).
+class TreeCompiler {
+ public:
+  TreeCompiler(const CatalogRelation &relation, std::function<bool(attribute_id)> has_nulls, std::function<bool(attribute_id)> expand_in,
+               TreeProgram *out)
+      : relation_(relation), has_nulls_(std::move(has_nulls)), expand_in_(std::move(expand_in)), out_(out) {}
+  void compile(const PredicateNode &root) {
+    walk(root);
+    // what qsx_bitmap_eval takes in one program
+    int depth = 0, deepest = 0;
+    for (std::int32_t code : out_->program) {
+      depth += code >= 0 ? 1 : (code == QSX_BOOL_NOT ? 0 : -1);
+      deepest = std::max(deepest, depth);
+    }
+    if (out_->leaves.size() > QSX_MAX_BOOL_LEAVES || out_->program.size() > QSX_MAX_BOOL_INSTRS || deepest > QSX_MAX_BOOL_DEPTH) {
+      throw ExecutionError("predicate tree: more than QSX_MAX_BOOL_LEAVES leaves, QSX_MAX_BOOL_INSTRS instructions or QSX_MAX_BOOL_DEPTH levels",
+                           QSX_ERR_UNSUPPORTED);
+    }
+  }
+
+ private:
+  void push(std::int32_t code) { out_->program.push_back(code); }
+  // Identical leaves are evaluated once; the same attribute's null bitmap is one leaf.
+  int termLeaf(const ComparisonPredicate &term) {
+    for (std::size_t k = 0; k < out_->leaves.size(); ++k) {
+      const TreeLeaf &l = out_->leaves[k];
+      if (l.null_of == kInvalidAttributeID && l.in == nullptr && l.term.attribute == term.attribute && l.term.comparison == term.comparison &&
+          SameLiteral(l.term.literal, term.literal)) {
+        return static_cast<int>(k);
+      }
+    }
+    TreeLeaf leaf;
+    leaf.term = term;
+    out_->leaves.push_back(leaf);
+    return static_cast<int>(out_->leaves.size() - 1);
+  }
+  int inLeaf(const PredicateNode &node, std::size_t begin, std::size_t end) {
+    for (std::size_t k = 0; k < out_->leaves.size(); ++k) {
+      const TreeLeaf &l = out_->leaves[k];
+      // the same attribute against the same literals in the same order, wherever in the tree the list was written
+      if (l.in == nullptr || l.term.attribute != node.comparison.attribute || l.in_end - l.in_begin != end - begin) continue;
+      bool same = true;
+      for (std::size_t i = 0; i < end - begin && same; ++i) same = SameLiteral((*l.in_source)[l.in_begin + i], node.in_literals[begin + i]);
+      if (same) return static_cast<int>(k);
+    }
+    TreeLeaf leaf;
+    leaf.term = node.comparison;
+    leaf.in = std::make_shared<InListLiterals>(MakeInList(relation_.getAttributeType(node.comparison.attribute), node.in_literals, begin, end));
+    leaf.in_source = &node.in_literals;
+    leaf.in_begin = begin;
+    leaf.in_end = end;
+    out_->leaves.push_back(leaf);
+    return static_cast<int>(out_->leaves.size() - 1);
+  }
+  // `value AND NOT null(a)`: a comparison with a NULL operand is not true (LiteralComparators-inl.hpp:330-370), whatever
+  // stands above it — so under a NOT the row IS selected (NegationPredicate.cpp:70-90)
+  void clearNulls(attribute_id a) {
+    if (!has_nulls_(a)) return;
+    int at = -1;
+    for (std::size_t k = 0; k < out_->leaves.size(); ++k) if (out_->leaves[k].null_of == a) at = static_cast<int>(k);
+    if (at < 0) {
+      TreeLeaf leaf;
+      leaf.null_of = a;
+      out_->leaves.push_back(leaf);
+      at = static_cast<int>(out_->leaves.size() - 1);
+    }
+    push(at);
+    push(QSX_BOOL_NOT);
+    push(QSX_BOOL_AND);
+  }
+  void walk(const PredicateNode &node) {
+    switch (node.kind) {
+      case PredicateNode::kComparison: {
+        if (node.comparison.rhs_attribute != kInvalidAttributeID) {
+          throw ExecutionError("predicate tree: a comparison of two attributes as a leaf", QSX_ERR_UNSUPPORTED);
+        }
+        push(termLeaf(node.comparison));
+        clearNulls(node.comparison.attribute);
+        return;
+      }
+      case PredicateNode::kInList: {
+        // InValueList::concretize (InValueList.cpp:40-65): a disjunction of equalities
+        const attribute_id a = node.comparison.attribute;
+        const Type &t = relation_.getAttributeType(a);
+        if (node.in_literals.empty()) throw ExecutionError("IN list without a literal", QSX_ERR_INVALID_ARGUMENT);
+        if (expand_in_(a)) {
+          for (std::size_t k = 0; k < node.in_literals.size(); ++k) {
+            if (node.in_literals[k].type != t.id) throw ExecutionError("IN list: a literal whose type differs from the operand's", QSX_ERR_UNSUPPORTED);
+            push(termLeaf(ComparisonPredicate(a, ComparisonID::kEqual, node.in_literals[k])));
+            if (k > 0) push(QSX_BOOL_OR);
+          }
+        } else {   // more than QSX_MAX_IN_LIST literals: several IN leaves under an OR
+          for (std::size_t begin = 0; begin < node.in_literals.size(); begin += QSX_MAX_IN_LIST) {
+            push(inLeaf(node, begin, std::min(node.in_literals.size(), begin + QSX_MAX_IN_LIST)));
+            if (begin > 0) push(QSX_BOOL_OR);
+          }
+        }
+        clearNulls(a);
+        return;
+      }
+      case PredicateNode::kNegation: {
+        if (node.children.size() != 1 || node.children[0] == nullptr) throw ExecutionError("predicate tree: NOT takes one child", QSX_ERR_INVALID_ARGUMENT);
+        walk(*node.children[0]);
+        push(QSX_BOOL_NOT);
+        return;
+      }
+      default: {
+        if (node.children.empty()) throw ExecutionError("predicate tree: AND / OR without a child", QSX_ERR_INVALID_ARGUMENT);
+        for (std::size_t k = 0; k < node.children.size(); ++k) {
+          if (node.children[k] == nullptr) throw ExecutionError("predicate tree: a null child", QSX_ERR_INVALID_ARGUMENT);
+          walk(*node.children[k]);
+          if (k > 0) push(node.kind == PredicateNode::kConjunction ? QSX_BOOL_AND : QSX_BOOL_OR);
+        }
+        return;
+      }
+    }
+  }
+  const CatalogRelation &relation_;
+  std::function<bool(attribute_id)> has_nulls_, expand_in_;
+  TreeProgram *out_;
+};
+
+void CollectLeafTerms(const PredicateNode &node, std::vector<const ComparisonPredicate *> *terms) {
+  if (node.kind == PredicateNode::kComparison || node.kind == PredicateNode::kInList) {
+    terms->push_back(&node.comparison);
+    return;
+  }
+  for (const PredicateNodePtr &child : node.children) if (child != nullptr) CollectLeafTerms(*child, terms);
+}
+
+typedef std::vector<std::unique_ptr<DeviceBuffer>> TermScratch;   // what queued kernels of a term still read
+
+// An IN list over a stripe of values (a column stripe, or a dictionary: then the result is that dictionary's code set).
+void SelectInList(const InListLiterals &in, const Type &t, const void *stripe, int char_width, std::int64_t n, const std::uint64_t *filter,
+                  std::uint64_t *out_bitmap, std::int64_t *out_count) {
+  if (t.id == kChar) {
+    CheckStatus(qsx_select_in_char(stripe, char_width, n, in.slots.data(), in.lengths.data(), in.count, 0, filter, out_bitmap, out_count, CurrentStream()),
+                "qsx_select_in_char");
+  } else {
+    CheckStatus(qsx_select_in(t.id, stripe, n, in.values.data(), in.count, 0, filter, out_bitmap, out_count, CurrentStream()), "qsx_select_in");
+  }
+}
+
+// ONE term over ONE block into a bitmap — the place both the conjunction chain and the leaves of a tree go through: plain
+// stripes, CHAR(n), LIKE, compressed attributes with the comparison rewritten on the block's codes, the search on the sort
+// column, and the code set of a LIKE or an IN list against the block's dictionary.  in != nullptr: `term.attribute IN (..)`.
+// NULLs are the caller's.
+void SelectTermForBlock(const StorageBlock &block, const ComparisonPredicate &term, const InListLiterals *in, const std::uint64_t *filter,
+                        std::uint64_t *out_bitmap, std::int64_t *out_count, TermScratch *scratch) {
+  const std::int64_t n = block.numTuples();
+  const Type &t = block.getRelation().getAttributeType(term.attribute);
+  const bool like = in == nullptr && IsLikeComparison(term.comparison);
+  if (like) CheckLikeTerm(term, t);
+  const CompressedAttribute *c = block.compressedAttribute(term.attribute);
+  if (c != nullptr && (like || (in != nullptr && c->kind == CompressedAttribute::kDictionary))) {
+    // LIKE / IN on a dictionary-coded attribute: the pattern or the list against the block's dictionary once (its matches are
+    // a set of codes), then code membership over the code stripe — on the sort column too, a set is no range.  The reference
+    // runs the matcher on every decompressed value (PatternMatchingComparators-inl.hpp:190-268); the values are not
+    // materialized here.
+    scratch->emplace_back(new DeviceBuffer(static_cast<std::size_t>((c->num_codes + 63) / 64) * 8 + 8));
+    std::uint64_t *set = static_cast<std::uint64_t *>(scratch->back()->ptr);
+    if (like) SelectCharTerm(term, c->dictionary, c->value_width, c->num_codes, nullptr, set, nullptr);
+    else SelectInList(*in, t, c->dictionary, c->value_width, c->num_codes, nullptr, set, nullptr);
+    CheckStatus(qsx_select_codes_in_set(c->code_width, c->codes, n, set, c->num_codes, filter, out_bitmap, out_count, CurrentStream()),
+                "qsx_select_codes_in_set");
+  } else if (c != nullptr) {
+    if (in != nullptr) throw ExecutionError("IN list over a truncated attribute reached the leaf evaluator", QSX_ERR_INVALID_ARGUMENT);
+    // CompressedTupleStorageSubBlock::getMatchesForPredicate (storage/CompressedTupleStorageSubBlock.cpp:160-250):
+    // rewrite to a comparison on codes, scan the code stripe
+    const PredicateTransformResult r = TransformPredicateOnCompressedAttribute(*c, t.id, term.comparison, term.literal);
+    if (r.type == PredicateTransformResult::kAll || r.type == PredicateTransformResult::kNone) {
+      // every code / no code: code >= 0 resp. code < 0
+      CheckStatus(qsx_select_codes(c->code_width, c->codes, n, r.type == PredicateTransformResult::kAll ? QSX_CODE_GE : QSX_CODE_LT, 0, 0,
+                                   filter, out_bitmap, out_count, CurrentStream()), "qsx_select_codes");
+    } else if (term.attribute == block.sortColumn()) {
+      // the sort column of a compressed store: the codes ascend, the matches are one range (the sort-column branches of
+      // CompressedColumnStoreTupleStorageSubBlock.cpp:420-760)
+      CheckStatus(qsx_select_codes_sorted(c->code_width, c->codes, n, r.comp, r.first_literal, r.second_literal, filter, out_bitmap, out_count,
+                                          CurrentStream()), "qsx_select_codes_sorted");
+    } else {
+      CheckStatus(qsx_select_codes(c->code_width, c->codes, n, r.comp, r.first_literal, r.second_literal, filter, out_bitmap, out_count,
+                                   CurrentStream()), "qsx_select_codes");
+    }
+  } else if (in != nullptr) {
+    SelectInList(*in, t, block.stripe(term.attribute), t.width, n, filter, out_bitmap, out_count);
+  } else if (t.id == kChar) {
+    SelectCharTerm(term, block.stripe(term.attribute), t.width, n, filter, out_bitmap, out_count);
+  } else if (term.attribute == block.sortColumn()) {
+    // the block is sorted on this attribute: SortColumnPredicateEvaluator (storage/ColumnStoreUtil.cpp:40-280)
+    CheckStatus(qsx_select_cmp_sorted(t.id, block.stripe(term.attribute), n, static_cast<int>(term.comparison), &term.literal.v, filter, out_bitmap,
+                                      out_count, CurrentStream()), "qsx_select_cmp_sorted");
+  } else {
+    CheckStatus(qsx_select_cmp(t.id, block.stripe(term.attribute), n, static_cast<int>(term.comparison), &term.literal.v, filter, out_bitmap,
+                               out_count, CurrentStream()), "qsx_select_cmp");
+  }
+}
+
+// The tree over one block: every leaf without a filter into a bitmap of its own, a nullable attribute's null bitmap as one more
+// leaf, one qsx_bitmap_eval behind `filter`.  What the queued kernels read goes to `scratch`.
+void EvaluateTreeForBlock(const PredicateNode &tree, const StorageBlock &block, const std::uint64_t *filter, std::uint64_t *out_bitmap,
+                          std::int64_t *out_count, TermScratch *scratch) {
+  const std::int64_t n = block.numTuples();
+  TreeProgram compiled;
+  TreeCompiler(block.getRelation(), [&](attribute_id a) { return block.nullBitmap(a) != nullptr; },
+               [&](attribute_id a) {
+                 const CompressedAttribute *c = block.compressedAttribute(a);
+                 return c != nullptr && c->kind != CompressedAttribute::kDictionary;
+               }, &compiled).compile(tree);
+  const std::size_t words = static_cast<std::size_t>((n + 63) / 64) + 1;
+  scratch->emplace_back(new DeviceBuffer(compiled.leaves.size() * words * 8 + 8));
+  std::uint64_t *next_leaf = static_cast<std::uint64_t *>(scratch->back()->ptr);
+  std::vector<const std::uint64_t *> leaves;
+  for (const TreeLeaf &leaf : compiled.leaves) {
+    if (leaf.null_of != kInvalidAttributeID) {
+      leaves.push_back(block.nullBitmap(leaf.null_of));
+      continue;
+    }
+    SelectTermForBlock(block, leaf.term, leaf.in.get(), nullptr, next_leaf, nullptr, scratch);
+    leaves.push_back(next_leaf);
+    next_leaf += words;
+  }
+  CheckStatus(qsx_bitmap_eval(static_cast<int>(leaves.size()), leaves.data(), static_cast<int>(compiled.program.size()), compiled.program.data(), n,
+                              filter, out_bitmap, out_count, CurrentStream()), "qsx_bitmap_eval");
+  ++tree_block_evaluations;
+}
+}  // namespace
+
+std::int64_t NumPredicateTreeBlockEvaluations() { return tree_block_evaluations.load(); }
+std::int64_t NumPredicateTreeRunEvaluations() { return tree_run_evaluations.load(); }
+
+void LowerPredicateToAggConfig(const Predicate &predicate, const CatalogRelation &relation, const std::function<int(attribute_id)> &column_of,
+                               qsx_agg_config_t *config, Predicate *external) {
+  const auto keep_out = [&](const char *what) {
+    if (external == nullptr) throw ExecutionError(std::string("qsx_agg_config_t.pred cannot hold ") + what, QSX_ERR_UNSUPPORTED);
+  };
+  int in_state = 0;
+  for (const ComparisonPredicate &term : predicate.conjuncts) {
+    const Type &t = relation.getAttributeType(term.attribute);
+    if (IsLikeComparison(term.comparison)) CheckLikeTerm(term, t);   // (a CHAR(n) term: evaluated by Predicate)
+    if (t.id == kChar || term.rhs_attribute != kInvalidAttributeID || in_state == QSX_MAX_PRED_TERMS) {
+      keep_out("a CHAR(n) term, a comparison of two attributes or more than QSX_MAX_PRED_TERMS terms");
+      external->conjuncts.push_back(term);   // string comparisons, attribute-vs-attribute, overflow
+      continue;
+    }
+    config->pred[in_state].column = column_of(term.attribute);
+    config->pred[in_state].op = static_cast<int>(term.comparison);
+    std::memcpy(&config->pred[in_state].literal, &term.literal.v, sizeof(term.literal.v));
+    ++in_state;
+  }
+  config->num_pred_terms = in_state;
+  if (predicate.tree != nullptr) {
+    // a tree (OR / NOT / IN) is no list of terms: it goes to the state's external predicate, evaluated block by block into the
+    // update's filter like CHAR(n) terms
+    keep_out("a predicate tree (OR / NOT / IN)");
+    external->tree = predicate.tree;
+  }
+}
+
 void *Predicate::getMatchesForBlock(const StorageBlock &block, std::int64_t *num_matches, const std::uint64_t *filter) const {
   const std::int64_t n = block.numTuples();
   const std::size_t words = static_cast<std::size_t>((n + 63) / 64);
@@ -36,77 +365,51 @@ void *Predicate::getMatchesForBlock(const StorageBlock &block, std::int64_t *num
   CheckStatus(qsx_device_alloc(8, &count), "qsx_device_alloc(count)");
   bool first = true;
   bool recount = false;
-  std::vector<std::unique_ptr<DeviceBuffer>> code_sets;   // (read by queued kernels: kept until the count has been read)
-  for (const ComparisonPredicate &term : conjuncts) {
-    const Type &t = block.getRelation().getAttributeType(term.attribute);
-    const std::uint64_t *in = first ? filter : static_cast<const std::uint64_t *>(current);
-    const bool like = IsLikeComparison(term.comparison);
-    if (like) CheckLikeTerm(term, t);
-    // conjunctions chain the filter through their children (short-circuit)
-    if (const CompressedAttribute *c = like ? block.compressedAttribute(term.attribute) : nullptr) {
-      // LIKE on a dictionary-coded attribute: the pattern against the block's dictionary once (its matches are a set of codes),
-      // then code membership over the code stripe — on the sort column too, a set is no range.  The reference runs the matcher
-      // on every decompressed value (PatternMatchingComparators-inl.hpp:190-268); the values are not materialized here.
-      code_sets.emplace_back(new DeviceBuffer(static_cast<std::size_t>((c->num_codes + 63) / 64) * 8 + 8));
-      std::uint64_t *set = static_cast<std::uint64_t *>(code_sets.back()->ptr);
-      SelectCharTerm(term, c->dictionary, c->value_width, c->num_codes, nullptr, set, nullptr);
-      CheckStatus(qsx_select_codes_in_set(c->code_width, c->codes, n, set, c->num_codes, in, static_cast<std::uint64_t *>(next),
-                                          static_cast<std::int64_t *>(count), CurrentStream()), "qsx_select_codes_in_set");
-    } else if (const CompressedAttribute *c = block.compressedAttribute(term.attribute)) {
-      // CompressedTupleStorageSubBlock::getMatchesForPredicate (storage/CompressedTupleStorageSubBlock.cpp:160-250):
-      // rewrite to a comparison on codes, scan the code stripe
-      const PredicateTransformResult r = TransformPredicateOnCompressedAttribute(*c, t.id, term.comparison, term.literal);
-      if (r.type == PredicateTransformResult::kAll || r.type == PredicateTransformResult::kNone) {
-        // every code / no code: code >= 0 resp. code < 0
-        CheckStatus(qsx_select_codes(c->code_width, c->codes, n, r.type == PredicateTransformResult::kAll ? QSX_CODE_GE : QSX_CODE_LT, 0, 0,
-                                     in, static_cast<std::uint64_t *>(next), static_cast<std::int64_t *>(count), CurrentStream()),
-                    "qsx_select_codes");
-      } else if (term.attribute == block.sortColumn()) {
-        // the sort column of a compressed store: the codes ascend, the matches are one range (the sort-column branches of
-        // CompressedColumnStoreTupleStorageSubBlock.cpp:420-760)
-        CheckStatus(qsx_select_codes_sorted(c->code_width, c->codes, n, r.comp, r.first_literal, r.second_literal, in,
-                                            static_cast<std::uint64_t *>(next), static_cast<std::int64_t *>(count), CurrentStream()),
-                    "qsx_select_codes_sorted");
-      } else {
-        CheckStatus(qsx_select_codes(c->code_width, c->codes, n, r.comp, r.first_literal, r.second_literal, in,
-                                     static_cast<std::uint64_t *>(next), static_cast<std::int64_t *>(count), CurrentStream()),
-                    "qsx_select_codes");
+  TermScratch scratch;   // code sets, leaf bitmaps (read by queued kernels: kept until the count has been read)
+  try {
+    for (const ComparisonPredicate &term : conjuncts) {
+      const std::uint64_t *in = first ? filter : static_cast<const std::uint64_t *>(current);
+      // conjunctions chain the filter through their children (short-circuit)
+      SelectTermForBlock(block, term, nullptr, in, static_cast<std::uint64_t *>(next), static_cast<std::int64_t *>(count), &scratch);
+      if (block.nullBitmap(term.attribute) != nullptr && n > 0) {
+        // a comparison with NULL is not true (LiteralComparators-inl.hpp:330-370: the nullable variants test the value
+        // pointer first): the stripe holds an arbitrary value under a NULL, so its match is taken back
+        CheckStatus(qsx_bitmap_combine(2, static_cast<const std::uint64_t *>(next), block.nullBitmap(term.attribute), n,
+                                       static_cast<std::uint64_t *>(next), CurrentStream()), "qsx_bitmap_combine");
+        recount = true;
       }
-    } else if (t.id == kChar) {
-      SelectCharTerm(term, block.stripe(term.attribute), t.width, n, in, static_cast<std::uint64_t *>(next), static_cast<std::int64_t *>(count));
-    } else if (term.attribute == block.sortColumn()) {
-      // the block is sorted on this attribute: SortColumnPredicateEvaluator (storage/ColumnStoreUtil.cpp:40-280)
-      CheckStatus(qsx_select_cmp_sorted(t.id, block.stripe(term.attribute), n, static_cast<int>(term.comparison), &term.literal.v, in,
-                                        static_cast<std::uint64_t *>(next), static_cast<std::int64_t *>(count), CurrentStream()),
-                  "qsx_select_cmp_sorted");
-    } else {
-      CheckStatus(qsx_select_cmp(t.id, block.stripe(term.attribute), n, static_cast<int>(term.comparison), &term.literal.v, in,
-                                 static_cast<std::uint64_t *>(next), static_cast<std::int64_t *>(count), CurrentStream()),
-                  "qsx_select_cmp");
+      std::swap(current, next);
+      first = false;
     }
-    if (block.nullBitmap(term.attribute) != nullptr && n > 0) {
-      // a comparison with NULL is not true (LiteralComparators-inl.hpp:330-370: the nullable variants test the value
-      // pointer first): the stripe holds an arbitrary value under a NULL, so its match is taken back
-      CheckStatus(qsx_bitmap_combine(2, static_cast<const std::uint64_t *>(next), block.nullBitmap(term.attribute), n,
-                                     static_cast<std::uint64_t *>(next), CurrentStream()), "qsx_bitmap_combine");
-      recount = true;
+    if (tree != nullptr) {
+      // AND(conjuncts) AND tree: the chain's result (or the incoming filter) is the evaluator's filter, applied once at the root —
+      // leaves are pure functions of the row, so this equals the reference's short-circuit filtering
+      EvaluateTreeForBlock(*tree, block, first ? filter : static_cast<const std::uint64_t *>(current), static_cast<std::uint64_t *>(next),
+                           static_cast<std::int64_t *>(count), &scratch);
+      std::swap(current, next);
+      first = false;
+      recount = false;   // (the evaluator counted)
     }
-    std::swap(current, next);
-    first = false;
+    if (recount) {
+      CheckStatus(qsx_bitmap_count(static_cast<const std::uint64_t *>(current), n, static_cast<std::int64_t *>(count), CurrentStream()),
+                  "qsx_bitmap_count");
+    }
+    if (first) {  // empty conjunction: every tuple (of the filter) matches
+      CheckStatus(qsx_memset_device(next, 0xFF, words * 8, CurrentStream()), "qsx_memset_device");
+      CheckStatus(qsx_bitmap_combine(0, static_cast<const std::uint64_t *>(next),
+                                     filter != nullptr ? filter : static_cast<const std::uint64_t *>(next), n,
+                                     static_cast<std::uint64_t *>(current), CurrentStream()), "qsx_bitmap_combine");
+      CheckStatus(qsx_bitmap_count(static_cast<const std::uint64_t *>(current), n, static_cast<std::int64_t *>(count),
+                                   CurrentStream()), "qsx_bitmap_count");
+    }
+    *num_matches = ReadCount(count);
+  } catch (...) {
+    qsx_stream_synchronize(CurrentStream());
+    qsx_device_free(current);
+    qsx_device_free(next);
+    qsx_device_free(count);
+    throw;
   }
-  if (recount) {
-    CheckStatus(qsx_bitmap_count(static_cast<const std::uint64_t *>(current), n, static_cast<std::int64_t *>(count), CurrentStream()),
-                "qsx_bitmap_count");
-  }
-  if (first) {  // empty conjunction: every tuple (of the filter) matches
-    CheckStatus(qsx_memset_device(next, 0xFF, words * 8, CurrentStream()), "qsx_memset_device");
-    CheckStatus(qsx_bitmap_combine(0, static_cast<const std::uint64_t *>(next),
-                                   filter != nullptr ? filter : static_cast<const std::uint64_t *>(next), n,
-                                   static_cast<std::uint64_t *>(current), CurrentStream()), "qsx_bitmap_combine");
-    CheckStatus(qsx_bitmap_count(static_cast<const std::uint64_t *>(current), n, static_cast<std::int64_t *>(count),
-                                 CurrentStream()), "qsx_bitmap_count");
-  }
-  *num_matches = ReadCount(count);
   qsx_device_free(next);
   qsx_device_free(count);
   return current;
@@ -115,17 +418,21 @@ void *Predicate::getMatchesForBlock(const StorageBlock &block, std::int64_t *num
 // ---------------------------------------------------------------------------
 // A predicate over a RUN of blocks (the SelectOperator's work orders over runs; the aggregation over runs of compressed blocks)
 // ---------------------------------------------------------------------------
-// Can the run forms evaluate `predicate` over these blocks in one launch per term?  Terms against a literal on attributes
-// without NULLs, every block coding and ordering a term's attribute like the first non-empty one.
+// Can the run forms evaluate `predicate` over these blocks in one launch per term?  Terms against a literal, every block coding
+// and ordering a term's attribute like the first non-empty one; a term of the conjunction chain on attributes without NULLs.
+// The leaves of a tree keep a nullable attribute on the run path: its null bitmap is one more leaf of the program, absent
+// (NULL) for the blocks that hold none.
 bool RunPredicateCovers(const Predicate &predicate, const std::vector<BlockReference> &blocks) {
   const StorageBlock *reference_block = nullptr;   // the first non-empty block: what the others have to agree with
+  std::vector<const ComparisonPredicate *> leaf_terms;
+  if (predicate.tree != nullptr) CollectLeafTerms(*predicate.tree, &leaf_terms);
   for (const BlockReference &block : blocks) {
     const StorageBlock &b = *block;
-    for (const ComparisonPredicate &term : predicate.conjuncts) {
+    const auto term_agrees = [&](const ComparisonPredicate &term, bool nulls_allowed, bool like) {
       const Type &t = b.getRelation().getAttributeType(term.attribute);
-      if (IsLikeComparison(term.comparison)) CheckLikeTerm(term, t);
-      if (term.rhs_attribute != kInvalidAttributeID || b.nullBitmap(term.attribute) != nullptr) return false;
-      if (b.numTuples() == 0) continue;                 // (an empty block has neither codes nor an order to agree on)
+      if (like) CheckLikeTerm(term, t);
+      if (term.rhs_attribute != kInvalidAttributeID || (!nulls_allowed && b.nullBitmap(term.attribute) != nullptr)) return false;
+      if (b.numTuples() == 0) return true;              // (an empty block has neither codes nor an order to agree on)
       // a term on the blocks' sort column is a per-block binary search (also on the code stripe of a compressed sort column), a
       // term on a compressed attribute a scan of the code stripes with the comparison rewritten per block
       if (t.id == kChar && b.compressedAttribute(term.attribute) == nullptr && term.attribute == b.sortColumn()) return false;
@@ -134,14 +441,143 @@ bool RunPredicateCovers(const Predicate &predicate, const std::vector<BlockRefer
       if ((term.attribute == b.sortColumn()) != (term.attribute == f.sortColumn())) return false;
       const CompressedAttribute *cb = b.compressedAttribute(term.attribute), *cf = f.compressedAttribute(term.attribute);
       if ((cb != nullptr) != (cf != nullptr) || (cb != nullptr && cb->code_width != cf->code_width)) return false;
+      return true;
+    };
+    for (const ComparisonPredicate &term : predicate.conjuncts) {
+      if (!term_agrees(term, false, IsLikeComparison(term.comparison))) return false;
+    }
+    for (const ComparisonPredicate *term : leaf_terms) {   // (an IN leaf's comparison is kEqual)
+      if (!term_agrees(*term, true, IsLikeComparison(term->comparison))) return false;
     }
   }
   return true;
 }
 
+namespace {
+// ONE term over a RUN of blocks, one launch (two for a code set): block b's bitmap into outs[b] behind in_filters[b].  The run
+// counterpart of SelectTermForBlock, used by the conjunction chain and by the leaves of a tree.  `ref`: the first non-empty
+// block (RunPredicateCovers made the others agree with it).
+void SelectTermForRun(const std::vector<BlockReference> &blocks, const std::vector<std::int64_t> &rows, const StorageBlock &ref,
+                      const ComparisonPredicate &term, const InListLiterals *in, const std::uint64_t *const *in_filters,
+                      std::uint64_t *const *outs, std::int64_t *counts, TermScratch *scratch) {
+  const std::size_t nb = blocks.size();
+  const Type &t = blocks.front()->getRelation().getAttributeType(term.attribute);
+  std::vector<const void *> stripes(nb);
+  if (ref.compressedAttribute(term.attribute) == nullptr) {   // (a compressed sort column is searched on its codes)
+    for (std::size_t b = 0; b < nb; ++b) stripes[b] = blocks[b]->stripe(term.attribute);
+  }
+  const bool like = in == nullptr && IsLikeComparison(term.comparison);
+  if (like) CheckLikeTerm(term, t);
+  const bool on_sort_column = term.attribute == ref.sortColumn();
+  // the comparison rewritten on every block's own codes (CompressedTupleStorageSubBlock::getMatchesForPredicate)
+  std::vector<std::int32_t> ops;
+  std::vector<std::uint32_t> firsts, seconds;
+  const auto rewrite_per_block = [&]() {
+    ops.resize(nb);
+    firsts.resize(nb);
+    seconds.resize(nb);
+    for (std::size_t b = 0; b < nb; ++b) {
+      const CompressedAttribute *c = blocks[b]->compressedAttribute(term.attribute);
+      if (c == nullptr) {   // an empty block
+        stripes[b] = nullptr;
+        ops[b] = QSX_CODE_LT;
+        firsts[b] = seconds[b] = 0;
+        continue;
+      }
+      const PredicateTransformResult r = TransformPredicateOnCompressedAttribute(*c, t.id, term.comparison, term.literal);
+      stripes[b] = c->codes;
+      if (r.type == PredicateTransformResult::kAll || r.type == PredicateTransformResult::kNone) {
+        ops[b] = r.type == PredicateTransformResult::kAll ? QSX_CODE_GE : QSX_CODE_LT;   // every code / no code
+        firsts[b] = seconds[b] = 0;
+      } else {
+        ops[b] = r.comp;
+        firsts[b] = r.first_literal;
+        seconds[b] = r.second_literal;
+      }
+    }
+  };
+  if ((like || in != nullptr) && ref.compressedAttribute(term.attribute) != nullptr) {
+    // LIKE / IN on a dictionary-coded attribute (the sort column included): one launch matches the pattern or the list against
+    // the run's dictionaries — block b's code set —, one tests the code stripes for membership in their block's set
+    std::vector<std::int64_t> dict_rows(nb, 0), num_codes(nb, 0);
+    std::vector<const void *> dictionaries(nb, nullptr);
+    std::vector<std::uint64_t *> sets(nb, nullptr);
+    std::size_t set_words = 0;
+    int value_width = t.width;
+    for (std::size_t b = 0; b < nb; ++b) {
+      const CompressedAttribute *c = blocks[b]->compressedAttribute(term.attribute);
+      stripes[b] = c != nullptr ? c->codes : nullptr;   // (nullptr: an empty block)
+      if (c == nullptr) continue;
+      dict_rows[b] = num_codes[b] = c->num_codes;
+      dictionaries[b] = c->dictionary;
+      value_width = c->value_width;
+      set_words += static_cast<std::size_t>((c->num_codes + 63) / 64) + 1;
+    }
+    scratch->emplace_back(new DeviceBuffer(set_words * 8 + 8));
+    std::size_t set_at = 0;
+    for (std::size_t b = 0; b < nb; ++b) {
+      sets[b] = static_cast<std::uint64_t *>(scratch->back()->ptr) + set_at;
+      set_at += static_cast<std::size_t>((num_codes[b] + 63) / 64) + (num_codes[b] != 0 ? 1 : 0);
+    }
+    if (like) {
+      CheckStatus(qsx_select_like_blocks(value_width, static_cast<std::int64_t>(nb), dict_rows.data(), dictionaries.data(), term.literal.text.data(),
+                                         static_cast<int>(term.literal.text.size()), term.comparison == ComparisonID::kNotLike ? 1 : 0, nullptr,
+                                         sets.data(), nullptr, CurrentStream()), "qsx_select_like_blocks");
+    } else if (t.id == kChar) {
+      CheckStatus(qsx_select_in_char_blocks(value_width, static_cast<std::int64_t>(nb), dict_rows.data(), dictionaries.data(), in->slots.data(),
+                                            in->lengths.data(), in->count, 0, nullptr, sets.data(), nullptr, CurrentStream()),
+                  "qsx_select_in_char_blocks");
+    } else {
+      CheckStatus(qsx_select_in_blocks(t.id, static_cast<std::int64_t>(nb), dict_rows.data(), dictionaries.data(), in->values.data(), in->count, 0,
+                                       nullptr, sets.data(), nullptr, CurrentStream()), "qsx_select_in_blocks");
+    }
+    CheckStatus(qsx_select_codes_in_set_blocks(ref.compressedAttribute(term.attribute)->code_width, static_cast<std::int64_t>(nb), rows.data(),
+                                               stripes.data(), sets.data(), num_codes.data(), in_filters, outs, counts, CurrentStream()),
+                "qsx_select_codes_in_set_blocks");
+  } else if (on_sort_column && ref.compressedAttribute(term.attribute) != nullptr) {
+    // the sort column of compressed blocks: the comparison rewritten on every block's own codes, then one search per block on
+    // the code stripes
+    rewrite_per_block();
+    CheckStatus(qsx_select_codes_sorted_blocks(ref.compressedAttribute(term.attribute)->code_width, static_cast<std::int64_t>(nb),
+                                               rows.data(), stripes.data(), ops.data(), firsts.data(), seconds.data(), in_filters, outs, counts,
+                                               CurrentStream()), "qsx_select_codes_sorted_blocks");
+  } else if (ref.compressedAttribute(term.attribute) != nullptr) {
+    // a compressed attribute: every block's code stripe scanned with the comparison rewritten on that block's codes
+    rewrite_per_block();
+    CheckStatus(qsx_select_codes_blocks(ref.compressedAttribute(term.attribute)->code_width, static_cast<std::int64_t>(nb), rows.data(),
+                                        stripes.data(), ops.data(), firsts.data(), seconds.data(), in_filters, outs, counts, CurrentStream()),
+                "qsx_select_codes_blocks");
+  } else if (in != nullptr && t.id == kChar) {
+    CheckStatus(qsx_select_in_char_blocks(t.width, static_cast<std::int64_t>(nb), rows.data(), stripes.data(), in->slots.data(), in->lengths.data(),
+                                          in->count, 0, in_filters, outs, counts, CurrentStream()), "qsx_select_in_char_blocks");
+  } else if (in != nullptr) {
+    CheckStatus(qsx_select_in_blocks(t.id, static_cast<std::int64_t>(nb), rows.data(), stripes.data(), in->values.data(), in->count, 0, in_filters,
+                                     outs, counts, CurrentStream()), "qsx_select_in_blocks");
+  } else if (like) {
+    // CHAR(n) LIKE pattern on plain stripes (PatternMatchingComparators-inl.hpp:190-268)
+    CheckStatus(qsx_select_like_blocks(t.width, static_cast<std::int64_t>(nb), rows.data(), stripes.data(), term.literal.text.data(),
+                                       static_cast<int>(term.literal.text.size()), term.comparison == ComparisonID::kNotLike ? 1 : 0, in_filters,
+                                       outs, counts, CurrentStream()), "qsx_select_like_blocks");
+  } else if (t.id == kChar) {
+    // CHAR(n) OP string literal on plain stripes (AsciiStringUncheckedComparator, AsciiStringComparators.hpp:218-251)
+    CheckStatus(qsx_select_cmp_char_blocks(t.width, static_cast<std::int64_t>(nb), rows.data(), stripes.data(), static_cast<int>(term.comparison),
+                                           term.literal.text.data(), static_cast<int>(term.literal.text.size()), in_filters, outs, counts,
+                                           CurrentStream()), "qsx_select_cmp_char_blocks");
+  } else if (on_sort_column) {
+    // SortColumnPredicateEvaluator (storage/ColumnStoreUtil.cpp:40-280), one search per block
+    CheckStatus(qsx_select_cmp_sorted_blocks(t.id, static_cast<std::int64_t>(nb), rows.data(), stripes.data(), static_cast<int>(term.comparison),
+                                             &term.literal.v, in_filters, outs, counts, CurrentStream()), "qsx_select_cmp_sorted_blocks");
+  } else {
+    CheckStatus(qsx_select_cmp_blocks(t.id, static_cast<std::int64_t>(nb), rows.data(), stripes.data(), static_cast<int>(term.comparison),
+                                      &term.literal.v, in_filters, outs, counts, CurrentStream()), "qsx_select_cmp_blocks");
+  }
+}
+}  // namespace
+
 // The TupleIdSequences of the run's blocks under `predicate` (RunPredicateCovers said yes), every term one launch over the run,
-// chained like a conjunction behind `in_filters` (per block, entries may be null; or nullptr): out->bitmaps[b] is block b's
-// bitmap, out->counts the per-block match counts of the last term (device memory).
+// chained like a conjunction behind `in_filters` (per block, entries may be null; or nullptr); then the tree: every leaf one
+// launch over the run into bitmaps of its own, and ONE qsx_bitmap_eval_blocks behind the chain's result.  out->bitmaps[b] is
+// block b's bitmap, out->counts the per-block match counts of the last launch (device memory).
 void RunPredicateMatches(const Predicate &predicate, const std::vector<BlockReference> &blocks, const std::vector<std::int64_t> &rows,
                          const std::uint64_t *const *in_filters, RunMatches *out) {
   const std::size_t nb = blocks.size();
@@ -162,120 +598,52 @@ void RunPredicateMatches(const Predicate &predicate, const std::vector<BlockRefe
     nxt[b] = static_cast<std::uint64_t *>(out->set_b->ptr) + at;
     at += static_cast<std::size_t>((rows[b] + 63) / 64) + 1;
   }
-  std::vector<const void *> stripes(nb);
   bool first = true;
   for (const ComparisonPredicate &term : predicate.conjuncts) {
-    const Type &t = blocks.front()->getRelation().getAttributeType(term.attribute);
-    const StorageBlock &ref = *reference_block;
-    if (ref.compressedAttribute(term.attribute) == nullptr) {   // (a compressed sort column is searched on its codes)
-      for (std::size_t b = 0; b < nb; ++b) stripes[b] = blocks[b]->stripe(term.attribute);
-    }
     const std::uint64_t *const *in = first ? in_filters : reinterpret_cast<const std::uint64_t *const *>(cur.data());
-    const bool on_sort_column = term.attribute == ref.sortColumn();
-    if (IsLikeComparison(term.comparison) && ref.compressedAttribute(term.attribute) != nullptr) {
-      // LIKE on a dictionary-coded attribute (the sort column included): one launch matches the pattern against the run's
-      // dictionaries — block b's code set —, one tests the code stripes for membership in their block's set
-      std::vector<std::int64_t> dict_rows(nb, 0), num_codes(nb, 0);
-      std::vector<const void *> dictionaries(nb, nullptr);
-      std::vector<std::uint64_t *> sets(nb, nullptr);
-      std::size_t set_words = 0;
-      int value_width = t.width;
-      for (std::size_t b = 0; b < nb; ++b) {
-        const CompressedAttribute *c = blocks[b]->compressedAttribute(term.attribute);
-        stripes[b] = c != nullptr ? c->codes : nullptr;   // (nullptr: an empty block)
-        if (c == nullptr) continue;
-        dict_rows[b] = num_codes[b] = c->num_codes;
-        dictionaries[b] = c->dictionary;
-        value_width = c->value_width;
-        set_words += static_cast<std::size_t>((c->num_codes + 63) / 64) + 1;
-      }
-      out->scratch.emplace_back(new DeviceBuffer(set_words * 8 + 8));
-      std::size_t set_at = 0;
-      for (std::size_t b = 0; b < nb; ++b) {
-        sets[b] = static_cast<std::uint64_t *>(out->scratch.back()->ptr) + set_at;
-        set_at += static_cast<std::size_t>((num_codes[b] + 63) / 64) + (num_codes[b] != 0 ? 1 : 0);
-      }
-      CheckStatus(qsx_select_like_blocks(value_width, static_cast<std::int64_t>(nb), dict_rows.data(), dictionaries.data(), term.literal.text.data(),
-                                         static_cast<int>(term.literal.text.size()), term.comparison == ComparisonID::kNotLike ? 1 : 0, nullptr,
-                                         sets.data(), nullptr, CurrentStream()), "qsx_select_like_blocks");
-      CheckStatus(qsx_select_codes_in_set_blocks(ref.compressedAttribute(term.attribute)->code_width, static_cast<std::int64_t>(nb), rows.data(),
-                                                 stripes.data(), sets.data(), num_codes.data(), in, nxt.data(),
-                                                 static_cast<std::int64_t *>(out->counts->ptr), CurrentStream()), "qsx_select_codes_in_set_blocks");
-    } else if (on_sort_column && ref.compressedAttribute(term.attribute) != nullptr) {
-      // the sort column of compressed blocks: the comparison rewritten on every block's own codes
-      // (CompressedTupleStorageSubBlock::getMatchesForPredicate), then one search per block on the code stripes
-      std::vector<std::int32_t> ops(nb);
-      std::vector<std::uint32_t> firsts(nb), seconds(nb);
-      for (std::size_t b = 0; b < nb; ++b) {
-        const CompressedAttribute *c = blocks[b]->compressedAttribute(term.attribute);
-        if (c == nullptr) {   // an empty block
-          stripes[b] = nullptr;
-          ops[b] = QSX_CODE_LT;
-          firsts[b] = seconds[b] = 0;
-          continue;
-        }
-        const PredicateTransformResult r = TransformPredicateOnCompressedAttribute(*c, t.id, term.comparison, term.literal);
-        stripes[b] = c->codes;
-        if (r.type == PredicateTransformResult::kAll || r.type == PredicateTransformResult::kNone) {
-          ops[b] = r.type == PredicateTransformResult::kAll ? QSX_CODE_GE : QSX_CODE_LT;   // every code / no code
-          firsts[b] = seconds[b] = 0;
-        } else {
-          ops[b] = r.comp;
-          firsts[b] = r.first_literal;
-          seconds[b] = r.second_literal;
-        }
-      }
-      CheckStatus(qsx_select_codes_sorted_blocks(ref.compressedAttribute(term.attribute)->code_width, static_cast<std::int64_t>(nb),
-                                                 rows.data(), stripes.data(), ops.data(), firsts.data(), seconds.data(), in, nxt.data(),
-                                                 static_cast<std::int64_t *>(out->counts->ptr), CurrentStream()), "qsx_select_codes_sorted_blocks");
-    } else if (ref.compressedAttribute(term.attribute) != nullptr) {
-      // a compressed attribute: every block's code stripe scanned with the comparison rewritten on that block's codes
-      std::vector<std::int32_t> ops(nb);
-      std::vector<std::uint32_t> firsts(nb), seconds(nb);
-      for (std::size_t b = 0; b < nb; ++b) {
-        const CompressedAttribute *c = blocks[b]->compressedAttribute(term.attribute);
-        if (c == nullptr) {   // an empty block
-          stripes[b] = nullptr;
-          ops[b] = QSX_CODE_LT;
-          firsts[b] = seconds[b] = 0;
-          continue;
-        }
-        const PredicateTransformResult r = TransformPredicateOnCompressedAttribute(*c, t.id, term.comparison, term.literal);
-        stripes[b] = c->codes;
-        if (r.type == PredicateTransformResult::kAll || r.type == PredicateTransformResult::kNone) {
-          ops[b] = r.type == PredicateTransformResult::kAll ? QSX_CODE_GE : QSX_CODE_LT;
-          firsts[b] = seconds[b] = 0;
-        } else {
-          ops[b] = r.comp;
-          firsts[b] = r.first_literal;
-          seconds[b] = r.second_literal;
-        }
-      }
-      CheckStatus(qsx_select_codes_blocks(ref.compressedAttribute(term.attribute)->code_width, static_cast<std::int64_t>(nb), rows.data(),
-                                          stripes.data(), ops.data(), firsts.data(), seconds.data(), in, nxt.data(),
-                                          static_cast<std::int64_t *>(out->counts->ptr), CurrentStream()), "qsx_select_codes_blocks");
-    } else if (IsLikeComparison(term.comparison)) {
-      // CHAR(n) LIKE pattern on plain stripes (PatternMatchingComparators-inl.hpp:190-268)
-      CheckStatus(qsx_select_like_blocks(t.width, static_cast<std::int64_t>(nb), rows.data(), stripes.data(), term.literal.text.data(),
-                                         static_cast<int>(term.literal.text.size()), term.comparison == ComparisonID::kNotLike ? 1 : 0, in,
-                                         nxt.data(), static_cast<std::int64_t *>(out->counts->ptr), CurrentStream()), "qsx_select_like_blocks");
-    } else if (t.id == kChar) {
-      // CHAR(n) OP string literal on plain stripes (AsciiStringUncheckedComparator, AsciiStringComparators.hpp:218-251)
-      CheckStatus(qsx_select_cmp_char_blocks(t.width, static_cast<std::int64_t>(nb), rows.data(), stripes.data(), static_cast<int>(term.comparison),
-                                             term.literal.text.data(), static_cast<int>(term.literal.text.size()), in, nxt.data(),
-                                             static_cast<std::int64_t *>(out->counts->ptr), CurrentStream()), "qsx_select_cmp_char_blocks");
-    } else if (on_sort_column) {
-      // SortColumnPredicateEvaluator (storage/ColumnStoreUtil.cpp:40-280), one search per block
-      CheckStatus(qsx_select_cmp_sorted_blocks(t.id, static_cast<std::int64_t>(nb), rows.data(), stripes.data(), static_cast<int>(term.comparison),
-                                               &term.literal.v, in, nxt.data(), static_cast<std::int64_t *>(out->counts->ptr), CurrentStream()),
-                  "qsx_select_cmp_sorted_blocks");
-    } else {
-      CheckStatus(qsx_select_cmp_blocks(t.id, static_cast<std::int64_t>(nb), rows.data(), stripes.data(), static_cast<int>(term.comparison),
-                                        &term.literal.v, in, nxt.data(), static_cast<std::int64_t *>(out->counts->ptr), CurrentStream()),
-                  "qsx_select_cmp_blocks");
-    }
+    SelectTermForRun(blocks, rows, *reference_block, term, nullptr, in, nxt.data(), static_cast<std::int64_t *>(out->counts->ptr), &out->scratch);
     std::swap(cur, nxt);
     first = false;
+  }
+  if (predicate.tree != nullptr && nb > 0) {
+    TreeProgram compiled;
+    TreeCompiler(blocks.front()->getRelation(),
+                 [&](attribute_id a) {
+                   for (const BlockReference &b : blocks) if (b->nullBitmap(a) != nullptr) return true;
+                   return false;
+                 },
+                 [&](attribute_id a) {   // one program for the run: equalities as soon as one block's codes are truncated values
+                   for (const BlockReference &b : blocks) {
+                     const CompressedAttribute *c = b->numTuples() > 0 ? b->compressedAttribute(a) : nullptr;
+                     if (c != nullptr && c->kind != CompressedAttribute::kDictionary) return true;
+                   }
+                   return false;
+                 }, &compiled).compile(*predicate.tree);
+    const std::size_t num_leaves = compiled.leaves.size();
+    out->scratch.emplace_back(new DeviceBuffer(num_leaves * bitmap_words * 8 + 8));
+    std::uint64_t *leaf_storage = static_cast<std::uint64_t *>(out->scratch.back()->ptr);
+    std::vector<const std::uint64_t *> block_leaves(nb * num_leaves, nullptr);
+    std::vector<std::uint64_t *> leaf_outs(nb);
+    for (std::size_t k = 0; k < num_leaves; ++k) {
+      const TreeLeaf &leaf = compiled.leaves[k];
+      if (leaf.null_of != kInvalidAttributeID) {   // (NULL for a block without a null bitmap: the all-zero leaf)
+        for (std::size_t b = 0; b < nb; ++b) block_leaves[b * num_leaves + k] = rows[b] > 0 ? blocks[b]->nullBitmap(leaf.null_of) : nullptr;
+        continue;
+      }
+      std::size_t leaf_at = k * bitmap_words;
+      for (std::size_t b = 0; b < nb; ++b) {
+        leaf_outs[b] = leaf_storage + leaf_at;
+        block_leaves[b * num_leaves + k] = rows[b] > 0 ? leaf_outs[b] : nullptr;
+        leaf_at += static_cast<std::size_t>((rows[b] + 63) / 64) + 1;
+      }
+      SelectTermForRun(blocks, rows, *reference_block, leaf.term, leaf.in.get(), nullptr, leaf_outs.data(), nullptr, &out->scratch);
+    }
+    const std::uint64_t *const *filters = first ? in_filters : reinterpret_cast<const std::uint64_t *const *>(cur.data());
+    CheckStatus(qsx_bitmap_eval_blocks(static_cast<int>(num_leaves), static_cast<int>(compiled.program.size()), compiled.program.data(),
+                                       static_cast<std::int64_t>(nb), rows.data(), block_leaves.data(), filters, nxt.data(),
+                                       static_cast<std::int64_t *>(out->counts->ptr), CurrentStream()), "qsx_bitmap_eval_blocks");
+    std::swap(cur, nxt);
+    ++tree_run_evaluations;
   }
   out->bitmaps = cur;
 }
@@ -657,8 +1025,11 @@ CaseEvaluator::CaseEvaluator(const ScalarPtr &s, const CatalogRelation &relation
     return flattener.add(value);
   };
   for (std::size_t k = 0; k < s->whens.size(); ++k) {
-    for (const ComparisonPredicate &term : s->whens[k].first.conjuncts) {
-      if (IsLikeComparison(term.comparison)) CheckLikeTerm(term, relation.getAttributeType(term.attribute));
+    std::vector<const ComparisonPredicate *> when_terms;
+    for (const ComparisonPredicate &term : s->whens[k].first.conjuncts) when_terms.push_back(&term);
+    if (s->whens[k].first.tree != nullptr) CollectLeafTerms(*s->whens[k].first.tree, &when_terms);
+    for (const ComparisonPredicate *term : when_terms) {
+      if (IsLikeComparison(term->comparison)) CheckLikeTerm(*term, relation.getAttributeType(term->attribute));
     }
     desc.value[k] = branch(s->whens[k].second);
   }
@@ -703,7 +1074,7 @@ bool CaseEvaluator::evalBlocks(const std::vector<BlockReference> &blocks, const 
                                std::vector<std::unique_ptr<RunMatches>> *keep) const {
   if (nullable || blocks.empty()) return false;
   for (const auto &when : scalar->whens) {
-    if (when.first.conjuncts.empty() || !RunPredicateCovers(when.first, blocks)) return false;
+    if (when.first.empty() || !RunPredicateCovers(when.first, blocks)) return false;
   }
   for (const BlockReference &b : blocks) {
     for (attribute_id a : attrs) if (b->nullBitmap(a) != nullptr) return false;
@@ -977,20 +1348,8 @@ AggregationOperationState::AggregationOperationState(const AggregationStateSpec 
   for (std::size_t k = 0; k < flattener.instrs().size(); ++k) config_.instrs[k] = flattener.instrs()[k];
   for (std::size_t k = 0; k < flattener.consts().size(); ++k) config_.consts[k] = flattener.consts()[k];
   if (spec.predicate != nullptr) {
-    int in_state = 0;
-    for (const ComparisonPredicate &term : spec.predicate->conjuncts) {
-      const Type &t = rel.getAttributeType(term.attribute);
-      if (IsLikeComparison(term.comparison)) CheckLikeTerm(term, t);   // (a CHAR(n) term: evaluated by Predicate, below)
-      if (t.id == kChar || term.rhs_attribute != kInvalidAttributeID || in_state == QSX_MAX_PRED_TERMS) {
-        external_predicate_.conjuncts.push_back(term);   // string comparisons, attribute-vs-attribute, overflow
-        continue;
-      }
-      config_.pred[in_state].column = column_of(term.attribute);
-      config_.pred[in_state].op = static_cast<int>(term.comparison);
-      std::memcpy(&config_.pred[in_state].literal, &term.literal.v, sizeof(term.literal.v));
-      ++in_state;
-    }
-    config_.num_pred_terms = in_state;
+    // (what the struct cannot hold — CHAR(n) terms, a tree — goes to external_predicate_: evaluated block by block by Predicate)
+    LowerPredicateToAggConfig(*spec.predicate, rel, [&](attribute_id a) { return column_of(a); }, &config_, &external_predicate_);
   }
   config_.num_columns = static_cast<int>(column_attr_.size());
   config_.est_groups = spec.estimated_num_groups;
@@ -1182,7 +1541,7 @@ void AggregationOperationState::aggregateBlock(const StorageBlock &block, const 
     void *ptr = nullptr;
     ~OwnedBitmap() { if (ptr != nullptr) qsx_device_free(ptr); }
   } external_matches;
-  if (!external_predicate_.conjuncts.empty() && n > 0) {
+  if (!external_predicate_.empty() && n > 0) {
     std::int64_t matches = 0;
     external_matches.ptr = external_predicate_.getMatchesForBlock(block, &matches, lip_filter);
     lip_filter = static_cast<const std::uint64_t *>(external_matches.ptr);
@@ -1299,7 +1658,7 @@ void AggregationOperationState::aggregateBlock(const StorageBlock &block, const 
 // its filter.  The state then has no predicate of its own, which also lets its aggregates factor through the dictionary codes
 // (csrc/agg_factored.hpp): TPC-H Q1's l_shipdate <= DATE over lineitem's compressed blocks.  Called with coded_mutex_ held.
 void AggregationOperationState::externalizeCodedPredicate() {
-  if (coded_config_.num_pred_terms > 0 && spec_.predicate != nullptr && external_predicate_.conjuncts.empty()) {
+  if (coded_config_.num_pred_terms > 0 && spec_.predicate != nullptr && external_predicate_.empty()) {
     coded_config_.num_pred_terms = 0;
     coded_predicate_external_ = true;
   }
@@ -1311,7 +1670,7 @@ void AggregationOperationState::externalizeCodedPredicate() {
 // ELSE 0 over non-nullable attributes) and the run forms cover the blocks; otherwise block by block, like nullable attributes.
 void AggregationOperationState::aggregateBlocksWithDerivedColumns(const std::vector<BlockReference> &blocks,
                                                         const std::vector<const std::uint64_t *> &lip_filters) {
-  bool in_run = state_ != nullptr && distinctify_.empty() && external_predicate_.conjuncts.empty();
+  bool in_run = state_ != nullptr && distinctify_.empty() && external_predicate_.empty();
   for (const auto &cc : case_columns_) in_run = in_run && !cc->evaluator.nullable;
   std::vector<BlockReference> run;
   std::vector<std::int64_t> rows;
@@ -1406,7 +1765,7 @@ void AggregationOperationState::aggregateBlocks(const std::vector<BlockReference
   std::vector<const std::uint64_t *> coded_filters;
   std::vector<BlockReference> coded_refs;
   bool any_coded_filter = false;
-  const bool state_allows = state_ != nullptr && distinctify_.empty() && external_predicate_.conjuncts.empty();
+  const bool state_allows = state_ != nullptr && distinctify_.empty() && external_predicate_.empty();
   // interned CHAR(n) keys: their id stripes are made for the whole run at once (internBlocks) and then stand where the
   // attribute's stripe would; until then the column's entry is a placeholder
   InternScratch intern_scratch;

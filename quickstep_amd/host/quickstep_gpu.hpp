@@ -338,7 +338,7 @@ struct TypedLiteral {
 };
 
 // ComparisonPredicate attr OP literal (expressions/predicate/ComparisonPredicate.cpp:115-334);
-// a Predicate is a conjunction of those.  As the residual predicate of a join
+// a Predicate is a conjunction of those and, optionally, a tree of them under AND / OR / NOT (PredicateNode).  As the residual predicate of a join
 // (HashJoinOperator.cpp:510-524, Predicate::matchesForJoinedTuples) a term also says which side each
 // attribute comes from (Scalar::kLeftSide = probe, kRightSide = build) and may compare two attributes.
 struct ComparisonPredicate {
@@ -358,12 +358,52 @@ struct ComparisonPredicate {
     return p;
   }
 };
+// A predicate TREE: comparisons and IN lists under AND / OR / NOT (expressions/predicate/ConjunctionPredicate.cpp,
+// DisjunctionPredicate.cpp:109-157, NegationPredicate.cpp:70-90; the optimizer's IN list, InValueList.cpp:40-65, which the
+// reference concretizes into a disjunction of equalities).  Two-valued, as the reference evaluates it: a leaf is not true for
+// a NULL operand (LiteralComparators-inl.hpp:330-370) and a negation inverts that, so NOT (x = 5) — and x NOT IN (..) —
+// SELECTS a row whose x is NULL.  This is the reference's behaviour, not SQL's three-valued logic.
+struct PredicateNode;
+typedef std::shared_ptr<const PredicateNode> PredicateNodePtr;
+struct PredicateNode {
+  enum Kind { kComparison, kInList, kConjunction, kDisjunction, kNegation };
+  Kind kind = kComparison;
+  ComparisonPredicate comparison;           // kComparison: attribute OP literal (LIKE included); kInList: `attribute` is the operand
+  std::vector<TypedLiteral> in_literals;    // kInList: literals of the operand's type, any number (at least one)
+  std::vector<PredicateNodePtr> children;   // kConjunction / kDisjunction: one or more; kNegation: exactly one
+};
 struct Predicate {
   std::vector<ComparisonPredicate> conjuncts;
+  // Optional.  The predicate is AND(conjuncts) AND tree: the conjuncts run first as a chain of selects behind the incoming
+  // filter (a range on the sort column stays a search), then every leaf of the tree is evaluated once, without a filter, into
+  // a bitmap of its own and ONE qsx_bitmap_eval combines them behind the chain's result.  A join's residual predicate and the
+  // terms a qsx_agg_config_t holds cannot carry a tree (QSX_ERR_UNSUPPORTED); an attribute-vs-attribute comparison cannot be a
+  // leaf; a tree whose program outgrows QSX_MAX_BOOL_LEAVES / _INSTRS / _DEPTH is QSX_ERR_UNSUPPORTED.
+  PredicateNodePtr tree = nullptr;
+  bool empty() const { return conjuncts.empty() && tree == nullptr; }
   // TupleIdSequence of the matching tuples of `block` (StorageBlock::getMatchesForPredicate), restricted to
   // `filter` when given.  Returns a device bitmap owned by the caller (qsx_device_free) and the match count.
   void *getMatchesForBlock(const StorageBlock &block, std::int64_t *num_matches, const std::uint64_t *filter = nullptr) const;
+  // Builders of tree nodes, and of a Predicate that is only a tree.
+  static PredicateNodePtr Compare(const ComparisonPredicate &term);
+  static PredicateNodePtr Compare(attribute_id a, ComparisonID c, const TypedLiteral &l) { return Compare(ComparisonPredicate(a, c, l)); }
+  static PredicateNodePtr In(attribute_id operand, std::vector<TypedLiteral> literals);
+  static PredicateNodePtr NotIn(attribute_id operand, std::vector<TypedLiteral> literals) { return Not(In(operand, std::move(literals))); }
+  static PredicateNodePtr And(std::vector<PredicateNodePtr> children);
+  static PredicateNodePtr Or(std::vector<PredicateNodePtr> children);
+  static PredicateNodePtr Not(PredicateNodePtr child);
+  static Predicate Tree(PredicateNodePtr root) { Predicate p; p.tree = std::move(root); return p; }
 };
+// How often a predicate tree was evaluated block by block (Predicate::getMatchesForBlock) and over a run of blocks (one
+// qsx_bitmap_eval_blocks) in this process: what a test reads to see that a run stayed on the run path.
+std::int64_t NumPredicateTreeBlockEvaluations();
+std::int64_t NumPredicateTreeRunEvaluations();
+// The terms of `predicate` a qsx_agg_config_t can hold (numeric attribute OP literal, at most QSX_MAX_PRED_TERMS) into
+// config->pred / num_pred_terms, columns named by column_of; everything else — CHAR(n) terms, attribute-vs-attribute, overflow,
+// a tree — into *external, to be evaluated by Predicate and handed to the update as its filter.  external == nullptr: the caller
+// has no such path, and a term or tree the struct cannot hold is QSX_ERR_UNSUPPORTED.
+void LowerPredicateToAggConfig(const Predicate &predicate, const CatalogRelation &relation, const std::function<int(attribute_id)> &column_of,
+                               qsx_agg_config_t *config, Predicate *external);
 
 // ---------------------------------------------------------------------------
 // InsertDestination (storage/InsertDestination.hpp:75-340): output sink
@@ -436,8 +476,8 @@ class Scalar {
   ScalarPtr left, right;
   // kCaseExpression — CASE WHEN p0 THEN e0 WHEN p1 THEN e1 .. ELSE e END (expressions/scalar/ScalarCaseExpression.cpp): the
   // first WHEN whose predicate holds gives the value; a null else_result is the NULL literal, as the resolver supplies it for
-  // an absent ELSE.  A WHEN is a Predicate, a conjunction: a disjunction of exclusive terms is written as several WHENs with
-  // the same result.  A CASE is the root of a Select scalar or of an aggregate's argument and nowhere else (inside an
+  // an absent ELSE.  A WHEN is a Predicate: a conjunction, a tree (Q12's o_orderpriority = '1-URGENT' OR o_orderpriority =
+  // '2-HIGH' is ONE WHEN), or both.  A CASE is the root of a Select scalar or of an aggregate's argument and nowhere else (inside an
   // arithmetic node or another CASE's branch: QSX_ERR_UNSUPPORTED); its branches are numeric (a CHAR attribute:
   // QSX_ERR_UNSUPPORTED); predicates and join projections hold attributes and literals only, so no CASE reaches them.
   std::vector<std::pair<Predicate, ScalarPtr>> whens;

@@ -84,7 +84,7 @@ void SelectWorkOrder::execute() {
 // terms like a conjunction), then the selected tuples of the run, block after block, are compacted into ONE output block
 // — what consecutive SelectWorkOrders do to an InsertDestination's current block (InsertDestination.cpp:222-260).
 bool SelectWorkOrder::executeRun() {
-  const bool has_terms = predicate_ != nullptr && !predicate_->conjuncts.empty();
+  const bool has_terms = predicate_ != nullptr && !predicate_->empty();
   // (no predicate and no filter: a projection of every tuple — the repartitioning Select in front of a partitioned join,
   // ExecutionGenerator's build / probe side "needs repartition" — takes the run form too: one compaction under all-ones
   // TupleIdSequences instead of a block allocation, a copy and a wait per 4 MB block)
@@ -391,6 +391,7 @@ void SelectWorkOrder::executeOnHost() {
   const std::int64_t n = block->numTuples();
   std::vector<bool> match(static_cast<std::size_t>(n), true);
   if (predicate_ != nullptr) {
+    if (predicate_->tree != nullptr) throw ExecutionError("a predicate tree (OR / NOT / IN) in the host plumbing mode", QSX_ERR_UNSUPPORTED);
     for (const ComparisonPredicate &term : predicate_->conjuncts) {
       const Type &t = block->getRelation().getAttributeType(term.attribute);
       if (IsLikeComparison(term.comparison)) throw ExecutionError("LIKE / NOT LIKE in the host plumbing mode", QSX_ERR_UNSUPPORTED);

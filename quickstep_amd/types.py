@@ -15,6 +15,10 @@ DATE = 6   # the reference's 8-byte DateLit {int32 year; uint8 month, day; 2 byt
 EQ, NE, LT, LE, GT, GE = range(6)
 CODE_EQ, CODE_NE, CODE_LT, CODE_GE, CODE_RANGE = range(5)            # qsx_code_cmp_t
 MAX_LIKE_PATTERN = 64                                               # QSX_MAX_LIKE_PATTERN (qsx_select_like)
+MAX_CHAR_LITERAL = 64                                               # QSX_MAX_CHAR_LITERAL (qsx_select_cmp_char, qsx_select_in_char)
+MAX_IN_LIST = 32                                                    # QSX_MAX_IN_LIST (qsx_select_in, qsx_select_in_char)
+MAX_BOOL_LEAVES, MAX_BOOL_INSTRS, MAX_BOOL_DEPTH = 32, 64, 8        # QSX_MAX_BOOL_* (qsx_bitmap_eval)
+BOOL_AND, BOOL_OR, BOOL_NOT = -1, -2, -3                            # QSX_BOOL_* postfix codes of qsx_bitmap_eval
 DATE_YEAR, DATE_MONTH = 0, 1                                        # QSX_DATE_YEAR / QSX_DATE_MONTH (qsx_eval_date_extract)
 # qsx_agg_strategy_t
 AGG_SINGLE_STATE, AGG_COMPACT_KEY, AGG_COLLISION_FREE, AGG_GENERIC = range(4)

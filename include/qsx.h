@@ -1024,7 +1024,15 @@ typedef struct qsx_agg_config {
                                              num_groups / finalize / export / merge.  Only when one update call spills more than
                                              the log holds (an estimate several orders of magnitude too low on a call of
                                              millions of rows) are rows lost: num_groups / finalize / export then return
-                                             QSX_ERR_TOO_MANY_GROUPS and the caller re-runs with a larger estimate. */
+                                             QSX_ERR_TOO_MANY_GROUPS and the caller re-runs with a larger estimate.
+                                             CLOSED states: a COMPACT_KEY state whose packed key code occupies at most 16 bits
+                                             (one or two CHAR(1) keys, one CHAR(2): TPC-H's flag and status columns) can hold
+                                             at most 2^bits groups whatever the estimate says.  Its table is created with
+                                             2^(bits+1) slots (when the estimate does not ask for more) — room for the whole
+                                             domain at a load no probe sequence can exhaust — and never overflows, spills
+                                             or grows: no spill log, and qsx_agg_finalize does not wait for the stream.  The
+                                             estimate still chooses the update kernels' geometry.  The exported image of
+                                             such a state has the size of that table (two CHAR(1) keys: 2^17 + 1 slots). */
   int64_t num_entries;                    /* COLLISION_FREE only: max_key + 1 (StarSchemaSimpleCostModel.cpp:707) */
   int32_t column_code_width[QSX_MAX_COLUMNS]; /* 0: the column arrives as values.  1 / 2 / 4: it arrives as a stripe of
                                              unsigned codes of that width (a compressed attribute of a
@@ -1190,9 +1198,15 @@ int qsx_agg_num_groups(qsx_agg_state_t *state, int64_t *out_groups, qsx_stream_t
  *                 caller reports QSX_ERR_HASH_COLLISION / re-runs the operator.  Expected once in ~2^64 / groups^2 states.
  * Every output row is defined by a successful call, whatever the buffers held before: rows [0, min(groups, capacity)) hold
  * the groups, rows [min(groups, capacity), capacity) of every key, value and null column are zero, and *out_groups_dev is
- * written (not added to) — the caller pre-zeroes nothing.  The call waits for `stream`: when it returns QSX_OK the
- * outputs are complete (a table that had to grow, or whose spill log had to drain, was finalized a second time over the
- * grown table before the call returned).  After an error return the outputs are undefined. */
+ * written (not added to) — the caller pre-zeroes nothing.
+ * The outputs are complete IN STREAM ORDER: work enqueued on `stream` behind the call sees them.  The call itself waits
+ * for `stream` only where the state may have to grow — a hash-strategy state sized from est_groups, whose table is then
+ * checked on the host (a table that had to grow, or whose spill log had to drain, is finalized a second time over the
+ * grown table before the call returns) and whose lost rows are reported as QSX_ERR_TOO_MANY_GROUPS.  A CLOSED state
+ * (see est_groups) has nothing to ask: the call enqueues its kernels and returns while they, and whatever was on the
+ * stream in front of them, are still pending.  A caller that reads the outputs FROM THE HOST must therefore order itself
+ * behind the stream (qsx_copy_to_host and qsx_stream_synchronize on the same stream do), for every strategy: which
+ * states wait is an implementation matter.  After an error return the outputs are undefined. */
 #define QSX_GROUPS_HASH_COLLISION (-1ll)
 int qsx_agg_finalize(qsx_agg_state_t *state, int partition, int num_partitions,
                      void *const *out_key_cols, void *const *out_val_cols,

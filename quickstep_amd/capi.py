@@ -1439,7 +1439,9 @@ class AggState:
 
     def finalize(self, device, partition=0, num_partitions=1, capacity=None, stream=None):
         """K10: returns (key columns, value columns, null columns (uint8), groups int64[1]).  qsx_agg_finalize defines every
-        output row — zero behind the groups — and the group count, so nothing is filled here."""
+        output row — zero behind the groups — and the group count, so nothing is filled here.  The tensors are complete in
+        stream order: the call returns without waiting where the state cannot grow (a closed key domain, include/qsx.h), so
+        reading them through torch on the same stream is ordered, and a caller that passes another `stream` waits for it."""
         cfg = self.config
         if capacity is None:
             capacity = max(self.num_groups(stream), 1)

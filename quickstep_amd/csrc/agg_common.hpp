@@ -176,7 +176,7 @@ __device__ __forceinline__ unsigned long long acc_combine(unsigned long long acc
 }
 
 // ---- global hash table --------------------------------------------------------
-__device__ __forceinline__ unsigned long long code_slot(unsigned long long code, int shift) {
+__host__ __device__ __forceinline__ unsigned long long code_slot(unsigned long long code, int shift) {
   return (mix64(code) * 0x9E3779B97F4A7C15ull) >> shift;
 }
 

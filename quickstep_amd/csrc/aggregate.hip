@@ -445,6 +445,60 @@ __global__ __launch_bounds__(kFinalizeBlockThreads) void finalize_hash_block_ker
   for (long long row = first + threadIdx.x; row < capacity; row += kFinalizeBlockThreads) zero_output_row(f, row);
 }
 
+// A closed state's table (qsx_agg_state: `closed`) is too large for one workgroup, and its finalize neither waits for the
+// host nor may cost a launch more than it has to: the rows are handed out from a cursor the STATE owns instead of
+// *out_groups, which would need zeroing in front of the launch.  The cursor is ONE word, zero between two finalizes: rows
+// handed out in its low half, workgroups done in its high half.  A workgroup adds its rows wave by wave, and behind a
+// barrier 2^32 for itself; all of that is relaxed atomics on one address, whose modification order agrees with the order
+// the barrier imposes — so the workgroup whose own addition completes the count reads, in that very addition's result, every
+// row handed out.  No fence: a device-scope fence per workgroup writes the L2 back each time (37.8 us for this kernel behind the
+// headline's update, against 13.5 without).  That last workgroup writes *out_groups, zeroes rows [groups, capacity) when `zero_tail`
+// says that few rows are one workgroup's work (finalize_tail_kernel follows otherwise) and puts the cursor back.  The other
+// workgroups' rows are none of its business: each wrote rows below the count.
+constexpr unsigned long long kCursorRowsMask = 0xFFFFFFFFull, kCursorWorkgroup = 1ull << 32;
+__global__ __launch_bounds__(kABlock) void finalize_hash_closed_kernel(HashTableView g, FinalizeDesc f, long long capacity,
+                                                                      unsigned long long *__restrict__ out_groups,
+                                                                      unsigned long long *cursor, int zero_tail) {
+  __shared__ unsigned long long s_found;
+  const unsigned long long stride = g.cap + 1;
+  const unsigned long long total = g.cap + 1;
+  const unsigned long long rounded = (total + kWave - 1) / kWave * kWave;
+  for (unsigned long long i = static_cast<unsigned long long>(blockIdx.x) * kABlock + threadIdx.x;
+       i < rounded; i += static_cast<unsigned long long>(gridDim.x) * kABlock) {
+    unsigned long long code = kEmptyCode;
+    const bool emit = i < total && slot_emits(g, f, i, 0, 1, 0, &code);
+    const uint64_t m = __ballot(emit);
+    if (m == 0) continue;
+    const int leader = __ffsll(static_cast<long long>(m)) - 1;
+    unsigned long long base = 0;
+    if (lane_id() == leader) {
+      base = __hip_atomic_fetch_add(cursor, static_cast<unsigned long long>(__popcll(m)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    base = __shfl(base, leader, kWave) & kCursorRowsMask;
+    if (!emit) continue;
+    const long long out_row = static_cast<long long>(base) + rank_below(m);
+    if (out_row >= capacity) continue;
+    write_keys_from_code(f, code, out_row, g.states, stride, i);
+    write_values(f, g.states, stride, i, 0, false, out_row);
+  }
+  __syncthreads();   // every wave's additions have returned
+  if (threadIdx.x == 0) {
+    const unsigned long long before = __hip_atomic_fetch_add(cursor, kCursorWorkgroup, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned long long found = ~0ull;   // (not the last workgroup)
+    if ((before >> 32) + 1 == gridDim.x) {
+      found = before & kCursorRowsMask;
+      *out_groups = found;
+      __hip_atomic_store(cursor, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    s_found = found;
+  }
+  __syncthreads();
+  const unsigned long long found = s_found;
+  if (found == ~0ull || zero_tail == 0) return;
+  const long long first = found < static_cast<unsigned long long>(capacity) ? static_cast<long long>(found) : capacity;
+  for (long long row = first + threadIdx.x; row < capacity; row += kABlock) zero_output_row(f, row);
+}
+
 // ---- K11 standalone: a scalar expression projected into a column (qsx_eval_expression) --------------------------------
 // The expression program of the aggregation kernel over global stripes instead of a staged tile: kExprRows rows per
 // thread, every node rounded on its own (-ffp-contract=off) like the reference's materialised temp vectors.
@@ -770,13 +824,18 @@ struct qsx_agg_state {
   size_t image_bytes = 0;
   unsigned long long cap = 0;      // hash strategies
   long long exist_words = 0;       // dense
-  // control words: [0] ngroups (u64), [1] overflow|error flag (int), [2] scratch counter, [3] spilled records (u32)
+  // control words: [0] ngroups (u64), [1] overflow|error flag (int), [2] scratch counter, [3] spilled records (u32),
+  // [4] wide-key collision flag, [5] row cursor of a closed state's finalize (finalize_hash_closed_kernel; zero between finalizes)
   unsigned long long *control = nullptr;
   // ---- growth (COMPACT_KEY / GENERIC) ----
   // Update / merge launches hold `table_mutex` shared (they read image, cap, geometry); growth holds it exclusive after
   // draining the device — the role of the reference's resize lock (storage/HashTable.hpp:1215 for the join table,
   // PackedPayloadHashTable::resize for this one).
   bool growable = false;
+  // A COMPACT_KEY state whose key code occupies at most kClosedKeyBits bits (closed_key_bits): the table has room for the
+  // whole key domain at a load no probe sequence can exhaust (closed_table_cap), so it never overflows, spills or grows —
+  // not growable, no spill log, no published words, and its finalize has nothing to ask the host (qsx_agg_finalize).
+  bool closed = false;
   mutable std::shared_mutex table_mutex;
   unsigned long long *log = nullptr;          // spill log, kLogRecords records of (num_cols + 1) words
   unsigned long long *published = nullptr;    // host-visible copy of {ngroups, spilled, overflow, seq} (publish_control_kernel)
@@ -912,6 +971,52 @@ static PublishedSlots &published_slots() {
   static PublishedSlots *slots = new PublishedSlots;   // (never destroyed: states may outlive static destruction order)
   return *slots;
 }
+
+// Closed key domains.  The bits the key code of a COMPACT_KEY plan occupies (its components lie at key_shift[], each
+// 8 * key_width[] bits wide), or 0 when the state is not closed: another strategy, a wide key, or more than kClosedKeyBits.
+// Two CHAR(1) keys — TPC-H Q1's flag and status — make 16 bits: at most 65 536 groups whatever the estimate says.
+constexpr int kClosedKeyBits = 16;
+static int closed_key_bits(const qsx_agg_config_t &c, const DevConfig &d) {
+  if (c.strategy != QSX_AGG_COMPACT_KEY || d.wide_words != 0 || d.num_keys < 1) return 0;
+  int bits = 0;
+  for (int k = 0; k < d.num_keys; ++k) bits = std::max(bits, d.key_shift[k] + 8 * d.key_width[k]);
+  return bits <= kClosedKeyBits ? bits : 0;
+}
+// Slots of a hash-strategy table created for `est` groups; key_bits != 0: of a closed state.  Twice the domain: linear
+// probing occupies the same set of slots in whatever order the keys arrive, and the set only grows with the key set, so a
+// table in which the WHOLE domain leaves no run of kGlobalMaxProbes occupied slots can never exhaust a probe sequence
+// (global_find_or_insert).  At 2^(b+1) slots the longest run of the full 16-bit domain is a few dozen; at 2^b the table
+// is full.  tests/cpp/closed_domain_test.cpp inserts every domain of 1..16 bits through code_slot and measures the run.
+static unsigned long long hash_table_cap(int64_t est, int key_bits) {
+  const unsigned long long by_estimate = next_pow2(static_cast<uint64_t>(est) * 8 + 1024);
+  return key_bits != 0 ? std::max(by_estimate, 1ull << (key_bits + 1)) : by_estimate;
+}
+static int64_t hash_table_estimate(const qsx_agg_config_t &c) {
+  return c.strategy == QSX_AGG_SINGLE_STATE ? 1 : (c.est_groups < 1 ? 1 : c.est_groups);
+}
+
+// Test hooks (not part of include/qsx.h; host arithmetic, no device): the closed-domain guarantee is checked against the
+// library's own hash and sizing.  Key bits (0: not closed) and slots of the table a state of this configuration gets ...
+extern "C" int qsx_debug_agg_table_geometry(const qsx_agg_config_t *config, int *out_closed_bits, unsigned long long *out_cap) {
+  if (config == nullptr || out_closed_bits == nullptr || out_cap == nullptr) return QSX_ERR_INVALID_ARGUMENT;
+  const Translated t = translate(*config);
+  if (t.status != QSX_OK) return t.status;
+  if (t.dense) return QSX_ERR_UNSUPPORTED;
+  *out_closed_bits = closed_key_bits(*config, t.dev);
+  *out_cap = hash_table_cap(hash_table_estimate(*config), *out_closed_bits);
+  return QSX_OK;
+}
+// ... the slots of a closed table over `key_bits` bits, the slot a code starts probing at in a table of `cap` slots (a
+// power of two), and how many slots a probe sequence visits before it gives up.
+extern "C" unsigned long long qsx_debug_agg_closed_cap(int64_t est_groups, int key_bits) {
+  return hash_table_cap(est_groups < 1 ? 1 : est_groups, key_bits);
+}
+extern "C" unsigned long long qsx_debug_agg_code_slot(unsigned long long code, unsigned long long cap) {
+  int log2 = 0;
+  while ((1ull << log2) < cap) ++log2;
+  return code_slot(code, 64 - log2);   // (the shift of qsx_agg_state::hash_view)
+}
+extern "C" unsigned long long qsx_debug_agg_max_probes(void) { return kGlobalMaxProbes; }
 
 // Fills the state from the constexpr-capable translation shared with the AOT plan shapes.
 static int translate_config(const qsx_agg_config_t &c, qsx_agg_state *st) {
@@ -2135,13 +2240,16 @@ int qsx_agg_state_create(const qsx_agg_config_t *config, qsx_agg_state_t **out) 
     st->image_bytes = sizeof(unsigned long long) * (st->exist_words + static_cast<size_t>(st->num_cols) * config->num_entries);
     st->max_tiles = (st->exist_words + kDenseTileWords - 1) / kDenseTileWords + 1;
   } else {
-    const int64_t est = config->strategy == QSX_AGG_SINGLE_STATE ? 1 : (config->est_groups < 1 ? 1 : config->est_groups);
+    const int64_t est = hash_table_estimate(*config);
     // generous head-room: the estimate comes from the optimizer and a table cannot be grown in the middle of a
-    // kernel — groups beyond it land in the spill log and the table grows before the next launch (maybe_grow / settle)
-    st->cap = next_pow2(static_cast<uint64_t>(est) * 8 + 1024);
+    // kernel — groups beyond it land in the spill log and the table grows before the next launch (maybe_grow / settle).
+    // A closed state holds its whole key domain instead; its LDS geometry and kernel choice still follow the estimate.
+    const int key_bits = closed_key_bits(*config, st->dev);
+    st->closed = key_bits != 0;
+    st->cap = hash_table_cap(est, key_bits);
     st->image_bytes = sizeof(unsigned long long) * (st->cap + 1) * (st->num_cols + 1);
     derive_geometry(st, est);
-    st->growable = config->strategy != QSX_AGG_SINGLE_STATE;
+    st->growable = config->strategy != QSX_AGG_SINGLE_STATE && !st->closed;
   }
   hipError_t err = device_malloc(reinterpret_cast<void **>(&st->image), st->image_bytes);
   if (err == hipSuccess) err = device_malloc(reinterpret_cast<void **>(&st->control), 8 * sizeof(unsigned long long));   // [4]: wide-key collision flag
@@ -4082,6 +4190,11 @@ static int launch_finalize(qsx_agg_state *st, const FinalizeDesc &f, int partiti
         hipLaunchKernelGGL(finalize_hash_block_kernel, dim3(1), dim3(kFinalizeBlockThreads), 0, s, st->hash_view(), f, generic ? partition : 0,
                            generic ? num_partitions : 1, generic ? 1 : 0, static_cast<long long>(capacity), out_groups, control_out);
         tail_done = true;
+      } else if (st->closed) {
+        // one launch (a second one for the tail of a large output): no zeroing of the count in front of it
+        tail_done = capacity <= kFinalizeBlockRows;
+        hipLaunchKernelGGL(finalize_hash_closed_kernel, dim3(grid_for(st->cap + 1, kABlock)), dim3(kABlock), 0, s, st->hash_view(), f,
+                           static_cast<long long>(capacity), out_groups, st->control + 5, tail_done ? 1 : 0);
       } else {
         QSX_HIP_TRY(hipMemsetAsync(out_groups_dev, 0, sizeof(int64_t), s));
         hipLaunchKernelGGL(finalize_hash_kernel, dim3(grid_for(st->cap + 1, kABlock)), dim3(kABlock), 0, s, st->hash_view(), f,
@@ -4162,6 +4275,15 @@ int qsx_agg_finalize(qsx_agg_state_t *st, int partition, int num_partitions, voi
     f.out_nulls[a] = out_null_cols != nullptr ? out_null_cols[a] : nullptr;
   }
   f.collision = reinterpret_cast<int *>(st->control + 4);
+  if (st->closed) {
+    // The question the wait below answers — did the table overflow, spill or pass load 1/4 — was settled when the state was
+    // created: enqueue and return.  The outputs are complete in stream order; the host runs ahead of the device.  (The
+    // calls that return a host value — num_groups, export, merge — still wait, and still report a raised overflow flag.)
+    if (!valid) return QSX_ERR_INVALID_ARGUMENT;
+    bool handed = false;
+    std::shared_lock<std::shared_mutex> lock(st->table_mutex);
+    return launch_finalize(st, f, partition, num_partitions, capacity, out_groups_dev, s, nullptr, &handed);
+  }
   // What settle() does, behind the finalize.  The hash-strategy kernels hand the control words over themselves, into
   // host-visible words that belong to this call; the other strategies' are copied.  Not published[]: that slot is the
   // state's, and a finalize of another partition that grows the table meanwhile (grow_and_drain stores the grown table's

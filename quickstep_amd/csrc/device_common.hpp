@@ -131,7 +131,9 @@ __device__ __forceinline__ bool compare_op(T a, int op, T b) {
 // relational_operators/tests/HashJoinOperator_unittest.cpp:480), so the device
 // tables are free not to use the reference's identity hash.
 __device__ __forceinline__ uint32_t mix32(uint32_t k) { return k * 0x9E3779B1u; }
-__device__ __forceinline__ uint64_t mix64(uint64_t k) {
+// (mix64 is callable from the host as well: the closed-domain guarantee of the aggregation's global table is checked
+// there against this very function, tests/cpp/closed_domain_test.cpp)
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t k) {
   k ^= k >> 32;
   k *= 0x9E3779B97F4A7C15ull;
   k ^= k >> 29;

@@ -336,6 +336,50 @@ int qsx_select_cmp_columns(int type, const void *lhs_dev, const void *rhs_dev, i
                            const uint64_t *filter_dev, uint64_t *out_bitmap_dev,
                            int64_t *out_count_dev, qsx_stream_t stream);
 
+/* Attribute OP attribute of ONE relation over a run of blocks in one launch, each operand read as its block holds it
+ * (TPC-H Q4 / Q12 / Q21: l_commitdate < l_receiptdate, l_shipdate < l_commitdate).  For every block b < num_blocks and
+ * every i < block_rows[b]:
+ *   block_out_bitmaps[b][i] = (value(lhs, b, i) OP value(rhs, b, i)) [AND block_filters[b][i]]
+ * Replaces LiteralUncheckedComparator<Functor, LeftCppType, .., RightCppType, ..>::compareSingleValueAccessor /
+ * compareColumnVectors (types/operations/comparisons/LiteralComparators-inl.hpp:52-125) as reached from
+ * ComparisonPredicate::getAllMatches (expressions/predicate/ComparisonPredicate.cpp:243-333), one SelectWorkOrder per
+ * block in the reference.
+ *   lhs_type, rhs_type  any pair of QSX_INT / QSX_LONG / QSX_FLOAT / QSX_DOUBLE (BasicComparison::
+ *               makeNumericComparatorInnerHelper instantiates all sixteen, BasicComparison.hpp:303-371), or QSX_DATE with
+ *               QSX_DATE (year, month, day; padding bytes ignored).  The functor is the C++ expression `left OP right`
+ *               (LiteralComparators.hpp:37-80), so the pair is compared under C++'s usual arithmetic conversions: INT with
+ *               LONG in int64, INT or LONG with FLOAT in float, anything with DOUBLE in double.  A NaN operand makes every
+ *               op false except QSX_NE; -0.0 == 0.0.  Any other pair, and QSX_CHAR: QSX_ERR_UNSUPPORTED.
+ *   block_lhs, block_rhs  host arrays of device pointers: each block's stripe of the operand (may be NULL for an empty block)
+ *   lhs_coding, rhs_coding  NULL (values of the operand's type in every block) or how each block holds the operand
+ *               (CompressedColumnStoreTupleStorageSubBlock compresses every block on its own; a run may mix codings from
+ *               block to block and between the two sides):
+ *                 block_code_width[b]    0: values; 1 / 2 / 4: a stripe of unsigned codes that wide
+ *                 block_dictionaries[b]  (the array itself may be NULL) NULL: the codes are truncated values (INT / LONG
+ *                                        only), widened without sign; else the block's dictionary of values of the
+ *                                        operand's type (QSX_DATE: 8-byte DateLit words) on the device
+ *                 block_num_codes[b]     entries of that dictionary.  A code >= block_num_codes[b] is the reference's NULL
+ *                                        code: the row compares false under every op, QSX_NE included, and the dictionary
+ *                                        is not read for it.  (Unused for values and truncated values.)
+ *   op, block_filters, block_out_bitmaps, out_counts_dev  as qsx_select_cmp_blocks: output words fully overwritten, bits
+ *               at positions >= block_rows[b] zero, NULL filter entries and empty blocks allowed
+ * QSX_ERR_INVALID_ARGUMENT, nothing written: negative rows, op outside QSX_EQ..QSX_GE, a code width other than
+ * 0 / 1 / 2 / 4, a dictionary without codes, truncation on a FLOAT / DOUBLE / DATE operand, a negative code count, a NULL
+ * stripe or bitmap of a non-empty block.  Without a device: QSX_ERR_NO_DEVICE in front of every other check.  Stripes may
+ * start at any multiple of 4 bytes.  The host arrays are consumed before the call returns.  QSX_ABI_VERSION did not
+ * change: a caller detects the capability by the presence of the symbol.  qsx_select_cmp_columns (one stripe, one type,
+ * values only) stays what join residuals on gathered pairs use. */
+typedef struct qsx_operand_coding {
+  const int32_t *block_code_width;        /* host [num_blocks]: 0 = values of the operand's type, 1, 2 or 4 = codes that wide */
+  const void *const *block_dictionaries;  /* NULL, or host [num_blocks] of device pointers; NULL entry = truncated values */
+  const int64_t *block_num_codes;         /* host [num_blocks]: entries of the block's dictionary (unused for truncation) */
+} qsx_operand_coding_t;
+int qsx_select_cmp_columns_blocks(int lhs_type, int rhs_type, int64_t num_blocks, const int64_t *block_rows,
+                                  const void *const *block_lhs, const qsx_operand_coding_t *lhs_coding,
+                                  const void *const *block_rhs, const qsx_operand_coding_t *rhs_coding, int op,
+                                  const uint64_t *const *block_filters, uint64_t *const *block_out_bitmaps,
+                                  int64_t *out_counts_dev, qsx_stream_t stream);
+
 /* ---- compressed attributes (CompressedColumnStoreTupleStorageSubBlock) ----------------------
  * An attribute of a compressed column-store block is a stripe of 1/2/4-byte unsigned CODES: the value
  * itself for a truncated INT/LONG attribute, or an index into a sorted dictionary

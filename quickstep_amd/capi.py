@@ -65,6 +65,7 @@ _SIGNATURES = {
     "qsx_select_cmp_sorted": (_int, [_int, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp]),
     "qsx_select_cmp_char": (_int, [_vp, _int, _i64, _int, C.c_char_p, _int, _vp, _vp, _vp, _vp]),
     "qsx_select_cmp_columns": (_int, [_int, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp]),
+    "qsx_select_cmp_columns_blocks": (_int, [_int, _int, _i64, C.POINTER(_i64), _pp, _vp, _pp, _vp, _int, _pp, _pp, _vp, _vp]),
     "qsx_select_like": (_int, [_vp, _int, _i64, C.c_char_p, _int, _int, _vp, _vp, _vp, _vp]),
     "qsx_select_in": (_int, [_int, _vp, _i64, _vp, _int, _int, _vp, _vp, _vp, _vp]),
     "qsx_select_in_blocks": (_int, [_int, _i64, C.POINTER(_i64), _pp, _vp, _int, _int, _pp, _pp, _vp, _vp]),
@@ -668,6 +669,52 @@ def select_cmp_columns(lhs, rhs, op, filter_bitmap=None, stream=None, qtype=None
     _check(_lib.qsx_select_cmp_columns(qsx_type_of(lhs) if qtype is None else qtype, _ptr(lhs), _ptr(rhs), n, op, _ptr(filter_bitmap),
                                        _ptr(out_bitmap), _ptr(out_count), _stream(stream)), "qsx_select_cmp_columns")
     return out_bitmap, out_count
+
+
+class OperandCoding(C.Structure):
+    """qsx_operand_coding_t: how every block of a run holds one operand of qsx_select_cmp_columns_blocks."""
+    _fields_ = [("block_code_width", C.POINTER(C.c_int32)), ("block_dictionaries", _pp), ("block_num_codes", C.POINTER(C.c_int64))]
+
+
+def _operand_coding(coding, nb):
+    """coding: None, or one (code_width, dictionary tensor or None[, num_codes]) per block; num_codes defaults to the
+    dictionary's length.  Returns (ctypes pointer or None, what must stay alive during the call)."""
+    if coding is None:
+        return None, None
+    assert len(coding) == nb
+    widths = (C.c_int32 * max(nb, 1))(*[int(c[0]) for c in coding])
+    dicts = (C.c_void_p * max(nb, 1))(*[None if c[1] is None else c[1].data_ptr() for c in coding])
+    counts = (C.c_int64 * max(nb, 1))(*[int(c[2]) if len(c) > 2 else (0 if c[1] is None else c[1].numel()) for c in coding])
+    desc = OperandCoding(widths, dicts, counts)
+    return C.byref(desc), (desc, widths, dicts, counts)
+
+
+def select_cmp_columns_blocks(lhs_blocks, rhs_blocks, op, lhs_type, rhs_type, lhs_coding=None, rhs_coding=None, filters=None, stream=None,
+                              out_bitmaps=None, counts=None, block_rows=None):
+    """K1, attribute OP attribute over a run of blocks in one launch, every operand as its block holds it (values, truncated
+    values or dictionary codes: *_coding as _operand_coding describes).  Returns (list of per-block bitmaps, counts int64[nb])
+    like select_cmp_blocks.  block_rows: rows per block when they cannot be read off the stripes (DATE stripes passed as
+    int64 and code stripes have one element per row, so it is rarely needed); counts=False: no counts."""
+    nb = len(lhs_blocks)
+    assert len(rhs_blocks) == nb
+    n_of = [t.numel() for t in lhs_blocks] if block_rows is None else list(block_rows)
+    dev = next((t.device for t in lhs_blocks if t is not None), None)
+    outs = out_bitmaps if out_bitmaps is not None else [new_bitmap(n, dev) for n in n_of]
+    if counts is None:
+        counts = torch.zeros(max(nb, 1), dtype=torch.int64, device=dev)
+    rows = (C.c_int64 * max(nb, 1))(*n_of)
+    lptr = (C.c_void_p * max(nb, 1))(*[t.data_ptr() if t is not None and t.numel() else None for t in lhs_blocks])
+    rptr = (C.c_void_p * max(nb, 1))(*[t.data_ptr() if t is not None and t.numel() else None for t in rhs_blocks])
+    optr = (C.c_void_p * max(nb, 1))(*[o.data_ptr() if o is not None and o.numel() else None for o in outs])
+    fptr = None
+    if filters is not None:
+        fptr = (C.c_void_p * max(nb, 1))(*[f.data_ptr() if f is not None and f.numel() else None for f in filters])
+    lcod, lkeep = _operand_coding(lhs_coding, nb)
+    rcod, rkeep = _operand_coding(rhs_coding, nb)
+    _check(_lib.qsx_select_cmp_columns_blocks(lhs_type, rhs_type, nb, rows, lptr, lcod, rptr, rcod, op, fptr, optr,
+                                              None if counts is False else _ptr(counts), _stream(stream)), "qsx_select_cmp_columns_blocks")
+    del lkeep, rkeep
+    return outs, (None if counts is False else counts[:nb])
 
 
 def select_codes(codes, op, first, second=0, filter_bitmap=None, stream=None):

@@ -54,8 +54,63 @@ PredicateNodePtr Predicate::And(std::vector<PredicateNodePtr> children) { return
 PredicateNodePtr Predicate::Or(std::vector<PredicateNodePtr> children) { return NodeOver(PredicateNode::kDisjunction, std::move(children)); }
 PredicateNodePtr Predicate::Not(PredicateNodePtr child) { return NodeOver(PredicateNode::kNegation, {std::move(child)}); }
 
+// attribute OP attribute outside a join residual: both attributes are the input relation's, numeric with numeric or DATE with DATE
+void CheckAttributeComparison(const ComparisonPredicate &term, const CatalogRelation &relation) {
+  if (term.on_build_side || term.rhs_on_build_side) {
+    throw ExecutionError("a comparison of two attributes names the build side outside a join residual", QSX_ERR_INVALID_ARGUMENT);
+  }
+  const Type &lhs = relation.getAttributeType(term.attribute), &rhs = relation.getAttributeType(term.rhs_attribute);
+  if (IsLikeComparison(term.comparison)) CheckLikeTerm(term, lhs);   // (LIKE / NOT LIKE between two attributes: refused there)
+  if (lhs.id == kChar || rhs.id == kChar) throw ExecutionError("a comparison of two attributes, one of them CHAR(n)", QSX_ERR_UNSUPPORTED);
+  if ((lhs.id == kDate) != (rhs.id == kDate)) throw ExecutionError("a comparison of a DATE attribute with an attribute that is no DATE", QSX_ERR_UNSUPPORTED);
+}
+
 namespace {
 std::atomic<std::int64_t> tree_block_evaluations{0}, tree_run_evaluations{0};
+std::atomic<std::int64_t> attribute_comparison_block_evaluations{0}, attribute_comparison_run_evaluations{0};
+
+// One side of `attribute OP attribute` over nb blocks as the blocks hold it (qsx_operand_coding_t): values, or the codes of a
+// compressed attribute with the block's code width, dictionary and number of codes — nothing is decoded.
+struct OperandOfBlocks {
+  std::vector<const void *> stripes, dictionaries;
+  std::vector<std::int32_t> code_widths;
+  std::vector<std::int64_t> num_codes;
+  qsx_operand_coding_t coding;
+  OperandOfBlocks(const StorageBlock *const *blocks, std::size_t nb, attribute_id a)
+      : stripes(nb, nullptr), dictionaries(nb, nullptr), code_widths(nb, 0), num_codes(nb, 0) {
+    for (std::size_t b = 0; b < nb; ++b) {
+      if (blocks[b]->numTuples() == 0) continue;
+      const CompressedAttribute *c = blocks[b]->compressedAttribute(a);
+      if (c == nullptr) {
+        stripes[b] = blocks[b]->stripe(a);
+        continue;
+      }
+      stripes[b] = c->codes;
+      code_widths[b] = c->code_width;
+      if (c->kind == CompressedAttribute::kDictionary) {
+        dictionaries[b] = c->dictionary;
+        num_codes[b] = c->num_codes;
+      }
+    }
+    coding.block_code_width = code_widths.data();
+    coding.block_dictionaries = dictionaries.data();
+    coding.block_num_codes = num_codes.data();
+  }
+};
+
+// term.attribute OP term.rhs_attribute over nb blocks in one launch (qsx_select_cmp_columns_blocks); a single block is a run of
+// one.  No sort-column case: a search does not apply to two attributes.  NULLs are the caller's.
+void SelectAttributeComparison(const StorageBlock *const *blocks, std::size_t nb, const std::int64_t *rows, const ComparisonPredicate &term,
+                               const std::uint64_t *const *in_filters, std::uint64_t *const *outs, std::int64_t *counts) {
+  if (nb == 0) return;
+  const CatalogRelation &relation = blocks[0]->getRelation();
+  CheckAttributeComparison(term, relation);
+  const OperandOfBlocks lhs(blocks, nb, term.attribute), rhs(blocks, nb, term.rhs_attribute);
+  CheckStatus(qsx_select_cmp_columns_blocks(relation.getAttributeType(term.attribute).id, relation.getAttributeType(term.rhs_attribute).id,
+                                            static_cast<std::int64_t>(nb), rows, lhs.stripes.data(), &lhs.coding, rhs.stripes.data(), &rhs.coding,
+                                            static_cast<int>(term.comparison), in_filters, outs, counts, CurrentStream()),
+              "qsx_select_cmp_columns_blocks");
+}
 
 // The literals of an IN leaf as the C ABI takes them (qsx_select_in / qsx_select_in_char): at most QSX_MAX_IN_LIST of them.
 struct InListLiterals {
@@ -248,6 +303,13 @@ void SelectInList(const InListLiterals &in, const Type &t, const void *stripe, i
 void SelectTermForBlock(const StorageBlock &block, const ComparisonPredicate &term, const InListLiterals *in, const std::uint64_t *filter,
                         std::uint64_t *out_bitmap, std::int64_t *out_count, TermScratch *scratch) {
   const std::int64_t n = block.numTuples();
+  if (in == nullptr && term.rhs_attribute != kInvalidAttributeID) {
+    // attribute OP attribute (ComparisonPredicate.cpp:243-333): both sides as the block holds them, the run form with one block
+    const StorageBlock *one = &block;
+    SelectAttributeComparison(&one, 1, &n, term, filter != nullptr ? &filter : nullptr, &out_bitmap, out_count);
+    ++attribute_comparison_block_evaluations;
+    return;
+  }
   const Type &t = block.getRelation().getAttributeType(term.attribute);
   const bool like = in == nullptr && IsLikeComparison(term.comparison);
   if (like) CheckLikeTerm(term, t);
@@ -327,6 +389,8 @@ void EvaluateTreeForBlock(const PredicateNode &tree, const StorageBlock &block, 
 
 std::int64_t NumPredicateTreeBlockEvaluations() { return tree_block_evaluations.load(); }
 std::int64_t NumPredicateTreeRunEvaluations() { return tree_run_evaluations.load(); }
+std::int64_t NumAttributeComparisonBlockEvaluations() { return attribute_comparison_block_evaluations.load(); }
+std::int64_t NumAttributeComparisonRunEvaluations() { return attribute_comparison_run_evaluations.load(); }
 
 void LowerPredicateToAggConfig(const Predicate &predicate, const CatalogRelation &relation, const std::function<int(attribute_id)> &column_of,
                                qsx_agg_config_t *config, Predicate *external) {
@@ -371,10 +435,12 @@ void *Predicate::getMatchesForBlock(const StorageBlock &block, std::int64_t *num
       const std::uint64_t *in = first ? filter : static_cast<const std::uint64_t *>(current);
       // conjunctions chain the filter through their children (short-circuit)
       SelectTermForBlock(block, term, nullptr, in, static_cast<std::uint64_t *>(next), static_cast<std::int64_t *>(count), &scratch);
-      if (block.nullBitmap(term.attribute) != nullptr && n > 0) {
-        // a comparison with NULL is not true (LiteralComparators-inl.hpp:330-370: the nullable variants test the value
-        // pointer first): the stripe holds an arbitrary value under a NULL, so its match is taken back
-        CheckStatus(qsx_bitmap_combine(2, static_cast<const std::uint64_t *>(next), block.nullBitmap(term.attribute), n,
+      // a comparison with NULL is not true (LiteralComparators-inl.hpp:330-370: the nullable variants test the value
+      // pointer first): the stripe holds an arbitrary value under a NULL, so its match is taken back — for either operand of a
+      // comparison of two attributes
+      for (const attribute_id a : {term.attribute, term.rhs_attribute}) {
+        if (a == kInvalidAttributeID || block.nullBitmap(a) == nullptr || n == 0) continue;
+        CheckStatus(qsx_bitmap_combine(2, static_cast<const std::uint64_t *>(next), block.nullBitmap(a), n,
                                        static_cast<std::uint64_t *>(next), CurrentStream()), "qsx_bitmap_combine");
         recount = true;
       }
@@ -431,7 +497,15 @@ bool RunPredicateCovers(const Predicate &predicate, const std::vector<BlockRefer
     const auto term_agrees = [&](const ComparisonPredicate &term, bool nulls_allowed, bool like) {
       const Type &t = b.getRelation().getAttributeType(term.attribute);
       if (like) CheckLikeTerm(term, t);
-      if (term.rhs_attribute != kInvalidAttributeID || (!nulls_allowed && b.nullBitmap(term.attribute) != nullptr)) return false;
+      if (term.rhs_attribute != kInvalidAttributeID) {
+        // attribute OP attribute: as a leaf it is refused (the per-block path says so); as a conjunct it stays on the run path —
+        // coding is per block and per side in qsx_select_cmp_columns_blocks, so the blocks need not agree on anything; a
+        // nullable operand sends the run to the per-block path like the other conjuncts
+        if (nulls_allowed) return false;
+        CheckAttributeComparison(term, b.getRelation());
+        return b.nullBitmap(term.attribute) == nullptr && b.nullBitmap(term.rhs_attribute) == nullptr;
+      }
+      if (!nulls_allowed && b.nullBitmap(term.attribute) != nullptr) return false;
       if (b.numTuples() == 0) return true;              // (an empty block has neither codes nor an order to agree on)
       // a term on the blocks' sort column is a per-block binary search (also on the code stripe of a compressed sort column), a
       // term on a compressed attribute a scan of the code stripes with the comparison rewritten per block
@@ -461,6 +535,14 @@ void SelectTermForRun(const std::vector<BlockReference> &blocks, const std::vect
                       const ComparisonPredicate &term, const InListLiterals *in, const std::uint64_t *const *in_filters,
                       std::uint64_t *const *outs, std::int64_t *counts, TermScratch *scratch) {
   const std::size_t nb = blocks.size();
+  if (in == nullptr && term.rhs_attribute != kInvalidAttributeID) {
+    // attribute OP attribute: one launch over the run, every block's two operands as that block holds them
+    std::vector<const StorageBlock *> plain(nb);
+    for (std::size_t b = 0; b < nb; ++b) plain[b] = blocks[b].get();
+    SelectAttributeComparison(plain.data(), nb, rows.data(), term, in_filters, outs, counts);
+    ++attribute_comparison_run_evaluations;
+    return;
+  }
   const Type &t = blocks.front()->getRelation().getAttributeType(term.attribute);
   std::vector<const void *> stripes(nb);
   if (ref.compressedAttribute(term.attribute) == nullptr) {   // (a compressed sort column is searched on its codes)
@@ -1030,6 +1112,7 @@ CaseEvaluator::CaseEvaluator(const ScalarPtr &s, const CatalogRelation &relation
     if (s->whens[k].first.tree != nullptr) CollectLeafTerms(*s->whens[k].first.tree, &when_terms);
     for (const ComparisonPredicate *term : when_terms) {
       if (IsLikeComparison(term->comparison)) CheckLikeTerm(*term, relation.getAttributeType(term->attribute));
+      if (term->rhs_attribute != kInvalidAttributeID) CheckAttributeComparison(*term, relation);
     }
     desc.value[k] = branch(s->whens[k].second);
   }

@@ -374,11 +374,16 @@ struct PredicateNode {
 };
 struct Predicate {
   std::vector<ComparisonPredicate> conjuncts;
+  // A conjunct may compare two attributes of the relation (ComparisonPredicate::Attributes; Q4 / Q12 / Q21's l_commitdate <
+  // l_receiptdate): any pair of INT / LONG / FLOAT / DOUBLE under C++'s usual arithmetic conversions, or DATE with DATE, both
+  // sides read as the block holds them (qsx_select_cmp_columns_blocks), a row with a NULL on either side not selected.  CHAR(n)
+  // operands, LIKE and DATE against a non-DATE are QSX_ERR_UNSUPPORTED; on_build_side / rhs_on_build_side set outside a join
+  // residual is QSX_ERR_INVALID_ARGUMENT.
   // Optional.  The predicate is AND(conjuncts) AND tree: the conjuncts run first as a chain of selects behind the incoming
   // filter (a range on the sort column stays a search), then every leaf of the tree is evaluated once, without a filter, into
   // a bitmap of its own and ONE qsx_bitmap_eval combines them behind the chain's result.  A join's residual predicate and the
   // terms a qsx_agg_config_t holds cannot carry a tree (QSX_ERR_UNSUPPORTED); an attribute-vs-attribute comparison cannot be a
-  // leaf; a tree whose program outgrows QSX_MAX_BOOL_LEAVES / _INSTRS / _DEPTH is QSX_ERR_UNSUPPORTED.
+  // LEAF (as a conjunct it can); a tree whose program outgrows QSX_MAX_BOOL_LEAVES / _INSTRS / _DEPTH is QSX_ERR_UNSUPPORTED.
   PredicateNodePtr tree = nullptr;
   bool empty() const { return conjuncts.empty() && tree == nullptr; }
   // TupleIdSequence of the matching tuples of `block` (StorageBlock::getMatchesForPredicate), restricted to
@@ -398,6 +403,10 @@ struct Predicate {
 // qsx_bitmap_eval_blocks) in this process: what a test reads to see that a run stayed on the run path.
 std::int64_t NumPredicateTreeBlockEvaluations();
 std::int64_t NumPredicateTreeRunEvaluations();
+// The same for a conjunct that compares two attributes: evaluated for one block (Predicate::getMatchesForBlock), and over a run
+// of blocks in one launch.
+std::int64_t NumAttributeComparisonBlockEvaluations();
+std::int64_t NumAttributeComparisonRunEvaluations();
 // The terms of `predicate` a qsx_agg_config_t can hold (numeric attribute OP literal, at most QSX_MAX_PRED_TERMS) into
 // config->pred / num_pred_terms, columns named by column_of; everything else — CHAR(n) terms, attribute-vs-attribute, overflow,
 // a tree — into *external, to be evaluated by Predicate and handed to the update as its filter.  external == nullptr: the caller

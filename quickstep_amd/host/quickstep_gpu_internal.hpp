@@ -289,6 +289,10 @@ struct RunMatches {
 // the ABI's op).
 inline bool IsLikeComparison(ComparisonID c) { return c == ComparisonID::kLike || c == ComparisonID::kNotLike; }
 void CheckLikeTerm(const ComparisonPredicate &term, const Type &type);
+// attribute OP attribute as a conjunct of a Select's, an aggregation's or a WHEN's predicate (query_context.cpp): throws unless both
+// attributes are `relation`'s own (no build side: QSX_ERR_INVALID_ARGUMENT), numeric with numeric or DATE with DATE, no LIKE
+// (QSX_ERR_UNSUPPORTED).
+void CheckAttributeComparison(const ComparisonPredicate &term, const CatalogRelation &relation);
 void SelectCharTerm(const ComparisonPredicate &term, const void *stripe, int width, std::int64_t n, const std::uint64_t *filter,
                     std::uint64_t *out_bitmap, std::int64_t *out_count);
 bool RunPredicateCovers(const Predicate &predicate, const std::vector<BlockReference> &blocks);

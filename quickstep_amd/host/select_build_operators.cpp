@@ -395,6 +395,7 @@ void SelectWorkOrder::executeOnHost() {
     for (const ComparisonPredicate &term : predicate_->conjuncts) {
       const Type &t = block->getRelation().getAttributeType(term.attribute);
       if (IsLikeComparison(term.comparison)) throw ExecutionError("LIKE / NOT LIKE in the host plumbing mode", QSX_ERR_UNSUPPORTED);
+      if (term.rhs_attribute != kInvalidAttributeID) throw ExecutionError("a comparison of two attributes in the host plumbing mode", QSX_ERR_UNSUPPORTED);
       const char *base = static_cast<const char *>(block->stripe(term.attribute));
       for (std::int64_t i = 0; i < n; ++i) {
         if (!match[i]) continue;

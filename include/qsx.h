@@ -209,6 +209,44 @@ int qsx_select_like_blocks(int width, int64_t num_blocks, const int64_t *block_r
                            const void *pattern, int pattern_length, int negate, const uint64_t *const *block_filters,
                            uint64_t *const *block_out_bitmaps, int64_t *out_counts_dev, qsx_stream_t stream);
 
+/* LIKE / NOT LIKE over a VARIABLE-LENGTH compression dictionary (a VARCHAR attribute of a CompressedColumnStore block):
+ * out_bitmap[e] = (match(entry e, pattern) XOR negate) [AND filter[e]] — the dictionary's code set for
+ * qsx_select_codes_in_set(_blocks).  Replaces the loop of PatternMatchingUncheckedComparator (PatternMatchingComparators-inl.hpp:
+ * 190-268) over the CompressedColumnStoreValueAccessor of such an attribute, which decompresses and matches every ROW
+ * (CompressedTupleStorageSubBlock::getAttributeValue, storage/CompressedTupleStorageSubBlock.hpp:225-300, into the matcher);
+ * here every dictionary ENTRY is matched once.
+ *   The dictionary is the reference's (compression/CompressionDictionary.hpp:46-58, CompressionDictionaryLite.hpp:248-290,
+ *   CompressionDictionaryBuilder.cpp:53-66): behind {uint32 num_codes; uint32 null_code} lie uint32 offset[num_codes], then the
+ *   value bytes back to back in code order.  Entry e is [offset[e], offset[e + 1]), the last one ends at value_bytes; a
+ *   VARCHAR value carries its terminating NUL (types/VarCharType.hpp:42,112), so an entry is 1 .. max_length + 1 bytes.
+ *   offsets_dev   the offset array, 4-byte aligned (an image may leave it at any alignment: copy it then)
+ *   values_dev    the first value byte, at ANY alignment: the bytes are read where they lie
+ *   num_entries   num_codes (the NULL code = num_codes has no entry and no bit)
+ *   value_bytes   bytes behind the offset array (dictionary size - 8 - 4 num_codes), at most 2^32 - 1
+ *   max_length    n of VARCHAR(n), 1 .. QSX_MAX_VARCHAR_LENGTH: the kernel's tile is sized from it.  An entry longer than
+ *                 max_length + 1 bytes, an offset beyond value_bytes or offsets that descend never make the kernel read outside
+ *                 the dictionary; the bits of such entries are unspecified (the host layer refuses such a block).
+ * Semantics are qsx_select_like's: the text of an entry ends at its first NUL, '%' matches any run of bytes, '_' one BYTE (the
+ * same UTF-8 deviation), no escape character, anchored at both ends, pattern_length 0 .. QSX_MAX_LIKE_PATTERN.  Bits at
+ * positions >= num_entries of the last word are zero, also under negate; out_count is overwritten.  Bad arguments as
+ * qsx_select_like (max_length < 1, value_bytes < num_entries, misaligned offsets: QSX_ERR_INVALID_ARGUMENT; max_length >
+ * QSX_MAX_VARCHAR_LENGTH or a pattern that is too long: QSX_ERR_UNSUPPORTED).  (TPC-H: p_type LIKE 'PROMO%', p_name LIKE
+ * '%green%', o_comment NOT LIKE '%special%requests%' — all VARCHAR in benchmarks/tpch/create.sql.)  QSX_ABI_VERSION did not
+ * change: a caller detects the capability by the presence of the symbols. */
+#define QSX_MAX_VARCHAR_LENGTH 255
+int qsx_select_like_var(const uint32_t *offsets_dev, const void *values_dev, int64_t num_entries, int64_t value_bytes, int max_length,
+                        const void *pattern, int pattern_length, int negate, const uint64_t *filter_dev, uint64_t *out_bitmap_dev,
+                        int64_t *out_count_dev, qsx_stream_t stream);
+
+/* qsx_select_like_var over the dictionaries of a run of blocks in one launch (every block of the reference has its own
+ * dictionary, CompressedTupleStorageSubBlock.cpp:160-250 runs per block): host arrays of per-block entry counts, offset arrays,
+ * value bytes and byte counts; one max_length for the run (it is the attribute's).  A block may have no entries.  filters,
+ * bitmaps and counts as qsx_select_like_blocks. */
+int qsx_select_like_var_blocks(int max_length, int64_t num_blocks, const int64_t *block_entries, const uint32_t *const *block_offsets,
+                               const void *const *block_values, const int64_t *block_value_bytes, const void *pattern,
+                               int pattern_length, int negate, const uint64_t *const *block_filters,
+                               uint64_t *const *block_out_bitmaps, int64_t *out_counts_dev, qsx_stream_t stream);
+
 /* K1 with an IN list on a numeric or DATE stripe: out_bitmap[i] = ((col[i] == some literal) XOR negate) [AND filter[i]], in one
  * pass over the column whatever the number of literals.  The reference's execution layer has no IN node: InValueList::concretize
  * (query_optimizer/expressions/InValueList.cpp:40-65) builds a disjunction of kEqual comparisons, which
@@ -465,6 +503,17 @@ int qsx_select_codes_sorted_blocks(int code_width, int64_t num_blocks, const int
  * projections). */
 int qsx_decode_codes(int code_width, const void *codes_dev, int64_t n, const void *dictionary_dev,
                      int value_width, void *out_dev, qsx_stream_t stream);
+
+/* Decode a code stripe over a VARIABLE-LENGTH dictionary (offsets_dev / values_dev / num_entries / value_bytes as for
+ * qsx_select_like_var) into fields of out_width (1 .. QSX_MAX_VARCHAR_LENGTH) bytes: row i of out is the text of entry
+ * codes[i] followed by NULs up to out_width bytes; a text of exactly out_width bytes has no terminator (the representation
+ * of CHAR(n)), a longer one is cut.  A code >= num_entries (the NULL code) gives an all-NUL field: the null bitmap is the
+ * caller's.  Replaces CompressedTupleStorageSubBlock::getAttributeValue (storage/CompressedTupleStorageSubBlock.hpp:225-300)
+ * over a variable-length dictionary (CompressionDictionaryLite::getUntypedValueForCode -> variableLengthGetUntypedValueHelper,
+ * CompressionDictionaryLite.hpp:248-290), per tuple in the reference, as qsx_decode_codes does for fixed dictionaries.
+ * code_width 1, 2 or 4 (else QSX_ERR_UNSUPPORTED). */
+int qsx_decode_codes_var(int code_width, const void *codes_dev, int64_t n, const uint32_t *offsets_dev, const void *values_dev,
+                         int64_t num_entries, int64_t value_bytes, int out_width, void *out_dev, qsx_stream_t stream);
 
 /* Bitmap algebra on TupleIdSequences of n bits (storage/TupleIdSequence.hpp:
  * intersectWith / unionWith / invert). op: 0 = AND, 1 = OR, 2 = AND NOT,

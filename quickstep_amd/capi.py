@@ -149,6 +149,9 @@ _SIGNATURES = {
     "qsx_select_cmp_char_blocks": (_int, [_int, _i64, C.POINTER(_i64), _pp, _int, _vp, _int, _pp, _pp, _vp, _vp]),
     "qsx_select_like_blocks": (_int, [_int, _i64, C.POINTER(_i64), _pp, C.c_char_p, _int, _int, _pp, _pp, _vp, _vp]),
     "qsx_select_codes_in_set_blocks": (_int, [_int, _i64, C.POINTER(_i64), _pp, _pp, C.POINTER(_i64), _pp, _pp, _vp, _vp]),
+    "qsx_select_like_var": (_int, [_vp, _vp, _i64, _i64, _int, C.c_char_p, _int, _int, _vp, _vp, _vp, _vp]),
+    "qsx_select_like_var_blocks": (_int, [_int, _i64, C.POINTER(_i64), _pp, _pp, C.POINTER(_i64), C.c_char_p, _int, _int, _pp, _pp, _vp, _vp]),
+    "qsx_decode_codes_var": (_int, [_int, _vp, _i64, _vp, _vp, _i64, _i64, _int, _vp, _vp]),
     "qsx_select_codes_blocks": (_int, [_int, _i64, C.POINTER(_i64), _pp, C.POINTER(_i32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _pp, _pp,
                                        _vp, _vp]),
     "qsx_select_codes_sorted_blocks": (_int, [_int, _i64, C.POINTER(_i64), _pp, C.POINTER(_i32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _pp, _pp,
@@ -646,6 +649,43 @@ def select_codes_in_set_blocks(code_blocks, code_sets, num_codes, filters=None, 
                                                (C.c_int64 * max(nb, 1))(*num_codes), fptr, optr, _ptr(counts), _stream(stream)),
            "qsx_select_codes_in_set_blocks")
     return outs, counts[:nb]
+
+
+def select_like_var(offsets, values, max_length, pattern, negate=False, filter_bitmap=None, stream=None, want_count=True):
+    """LIKE (negate: NOT LIKE) over a variable-length dictionary: offsets = int32 tensor of num_entries offsets (their bits are
+    the dictionary's uint32), values = uint8 tensor of the value bytes (a slice at any alignment), max_length = n of VARCHAR(n).
+    Returns (bitmap of num_entries bits — the code set for select_codes_in_set —, count or None)."""
+    assert offsets.dtype == torch.int32 and values.dtype == torch.uint8 and values.is_contiguous()
+    n = offsets.numel()
+    out_bitmap = new_bitmap(n, values.device)
+    out_count = torch.zeros(1, dtype=torch.int64, device=values.device) if want_count else None
+    _check(_lib.qsx_select_like_var(_ptr(offsets), _ptr(values), n, values.numel(), max_length, C.c_char_p(pattern), len(pattern),
+                                    int(negate), _ptr(filter_bitmap), _ptr(out_bitmap), _ptr(out_count), _stream(stream)),
+           "qsx_select_like_var")
+    return out_bitmap, out_count
+
+
+def select_like_var_blocks(offsets, values, max_length, pattern, negate=False, filters=None, stream=None):
+    """select_like_var over the dictionaries of a run of blocks in one launch: offsets / values = one tensor per block (a block
+    may have no entries).  Returns (per-block bitmaps, counts int64[nb])."""
+    nb, outs, counts, rows, _, optr, fptr = _run_outputs(offsets, filters)
+    vptr = (C.c_void_p * max(nb, 1))(*[v.data_ptr() if v.numel() else None for v in values])
+    fixed = (C.c_void_p * max(nb, 1))(*[o.data_ptr() if o.numel() else None for o in offsets])
+    nbytes = (C.c_int64 * max(nb, 1))(*[v.numel() for v in values])
+    _check(_lib.qsx_select_like_var_blocks(max_length, nb, rows, fixed, vptr, nbytes, C.c_char_p(pattern), len(pattern), int(negate), fptr,
+                                           optr, _ptr(counts), _stream(stream)), "qsx_select_like_var_blocks")
+    return outs, counts[:nb]
+
+
+def decode_codes_var(codes, offsets, values, out_width, stream=None, out=None):
+    """codes over a variable-length dictionary (offsets, values as select_like_var) -> uint8 tensor (n, out_width) of NUL-padded
+    fields; a code >= the number of entries (the NULL code) gives an all-NUL field."""
+    assert offsets.dtype == torch.int32 and values.dtype == torch.uint8 and values.is_contiguous()
+    if out is None:
+        out = torch.empty((codes.numel(), out_width), dtype=torch.uint8, device=codes.device)
+    _check(_lib.qsx_decode_codes_var(codes.element_size(), _ptr(codes), codes.numel(), _ptr(offsets), _ptr(values), offsets.numel(),
+                                     values.numel(), out_width, _ptr(out), _stream(stream)), "qsx_decode_codes_var")
+    return out
 
 
 def select_cmp_sorted(col, op, literal, filter_bitmap=None, stream=None, qtype=None):

@@ -282,6 +282,7 @@ void SortBlocksInto(const std::vector<BlockReference> &blocks, const CatalogRela
   for (std::size_t k = 0; k < config.order_by.size(); ++k) {
     const attribute_id a = config.order_by[k];
     const Type &type = relation.getAttributeType(a);
+    if (type.id == kVarChar) throw ExecutionError("a VARCHAR attribute as an ORDER BY key", QSX_ERR_UNSUPPORTED);
     qsx_sort_key_t key{};
     key.col_dev = stripes.at(a);
     key.type = type.id;

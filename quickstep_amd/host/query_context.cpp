@@ -7,7 +7,7 @@ namespace quickstep {
 // Predicate
 // ---------------------------------------------------------------------------
 void CheckLikeTerm(const ComparisonPredicate &term, const Type &type) {
-  if (type.id != kChar) throw ExecutionError("LIKE / NOT LIKE on an attribute that is not CHAR(n)", QSX_ERR_UNSUPPORTED);
+  if (!IsTextType(type.id)) throw ExecutionError("LIKE / NOT LIKE on an attribute that is neither CHAR(n) nor VARCHAR(n)", QSX_ERR_UNSUPPORTED);
   if (term.rhs_attribute != kInvalidAttributeID) throw ExecutionError("LIKE / NOT LIKE between two attributes", QSX_ERR_UNSUPPORTED);
   if (term.literal.text.size() > QSX_MAX_LIKE_PATTERN) throw ExecutionError("LIKE pattern longer than QSX_MAX_LIKE_PATTERN bytes", QSX_ERR_UNSUPPORTED);
 }
@@ -61,6 +61,7 @@ void CheckAttributeComparison(const ComparisonPredicate &term, const CatalogRela
   }
   const Type &lhs = relation.getAttributeType(term.attribute), &rhs = relation.getAttributeType(term.rhs_attribute);
   if (IsLikeComparison(term.comparison)) CheckLikeTerm(term, lhs);   // (LIKE / NOT LIKE between two attributes: refused there)
+  if (lhs.id == kVarChar || rhs.id == kVarChar) throw ExecutionError("a comparison of two attributes, one of them VARCHAR(n)", QSX_ERR_UNSUPPORTED);
   if (lhs.id == kChar || rhs.id == kChar) throw ExecutionError("a comparison of two attributes, one of them CHAR(n)", QSX_ERR_UNSUPPORTED);
   if ((lhs.id == kDate) != (rhs.id == kDate)) throw ExecutionError("a comparison of a DATE attribute with an attribute that is no DATE", QSX_ERR_UNSUPPORTED);
 }
@@ -238,6 +239,7 @@ class TreeCompiler {
         const attribute_id a = node.comparison.attribute;
         const Type &t = relation_.getAttributeType(a);
         if (node.in_literals.empty()) throw ExecutionError("IN list without a literal", QSX_ERR_INVALID_ARGUMENT);
+        if (t.id == kVarChar) throw ExecutionError("IN list on a VARCHAR attribute", QSX_ERR_UNSUPPORTED);
         if (expand_in_(a)) {
           for (std::size_t k = 0; k < node.in_literals.size(); ++k) {
             if (node.in_literals[k].type != t.id) throw ExecutionError("IN list: a literal whose type differs from the operand's", QSX_ERR_UNSUPPORTED);
@@ -321,8 +323,18 @@ void SelectTermForBlock(const StorageBlock &block, const ComparisonPredicate &te
     // materialized here.
     scratch->emplace_back(new DeviceBuffer(static_cast<std::size_t>((c->num_codes + 63) / 64) * 8 + 8));
     std::uint64_t *set = static_cast<std::uint64_t *>(scratch->back()->ptr);
-    if (like) SelectCharTerm(term, c->dictionary, c->value_width, c->num_codes, nullptr, set, nullptr);
-    else SelectInList(*in, t, c->dictionary, c->value_width, c->num_codes, nullptr, set, nullptr);
+    if (c->variable_length) {
+      // a VARCHAR attribute: the pattern against the entries of the variable-length dictionary where the image holds them
+      if (!like) throw ExecutionError("IN list on a VARCHAR attribute", QSX_ERR_UNSUPPORTED);
+      CheckStatus(qsx_select_like_var(c->variable_offsets, c->variable_values, c->num_codes, static_cast<std::int64_t>(c->variable_value_bytes),
+                                      t.width, term.literal.text.data(), static_cast<int>(term.literal.text.size()),
+                                      term.comparison == ComparisonID::kNotLike ? 1 : 0, nullptr, set, nullptr, CurrentStream()),
+                  "qsx_select_like_var");
+    } else if (like) {
+      SelectCharTerm(term, c->dictionary, c->value_width, c->num_codes, nullptr, set, nullptr);
+    } else {
+      SelectInList(*in, t, c->dictionary, c->value_width, c->num_codes, nullptr, set, nullptr);
+    }
     CheckStatus(qsx_select_codes_in_set(c->code_width, c->codes, n, set, c->num_codes, filter, out_bitmap, out_count, CurrentStream()),
                 "qsx_select_codes_in_set");
   } else if (c != nullptr) {
@@ -345,7 +357,7 @@ void SelectTermForBlock(const StorageBlock &block, const ComparisonPredicate &te
     }
   } else if (in != nullptr) {
     SelectInList(*in, t, block.stripe(term.attribute), t.width, n, filter, out_bitmap, out_count);
-  } else if (t.id == kChar) {
+  } else if (IsTextType(t.id)) {   // (a plain VARCHAR(n) stripe holds CHAR(n) fields)
     SelectCharTerm(term, block.stripe(term.attribute), t.width, n, filter, out_bitmap, out_count);
   } else if (term.attribute == block.sortColumn()) {
     // the block is sorted on this attribute: SortColumnPredicateEvaluator (storage/ColumnStoreUtil.cpp:40-280)
@@ -401,7 +413,7 @@ void LowerPredicateToAggConfig(const Predicate &predicate, const CatalogRelation
   for (const ComparisonPredicate &term : predicate.conjuncts) {
     const Type &t = relation.getAttributeType(term.attribute);
     if (IsLikeComparison(term.comparison)) CheckLikeTerm(term, t);   // (a CHAR(n) term: evaluated by Predicate)
-    if (t.id == kChar || term.rhs_attribute != kInvalidAttributeID || in_state == QSX_MAX_PRED_TERMS) {
+    if (IsTextType(t.id) || term.rhs_attribute != kInvalidAttributeID || in_state == QSX_MAX_PRED_TERMS) {
       keep_out("a CHAR(n) term, a comparison of two attributes or more than QSX_MAX_PRED_TERMS terms");
       external->conjuncts.push_back(term);   // string comparisons, attribute-vs-attribute, overflow
       continue;
@@ -509,7 +521,7 @@ bool RunPredicateCovers(const Predicate &predicate, const std::vector<BlockRefer
       if (b.numTuples() == 0) return true;              // (an empty block has neither codes nor an order to agree on)
       // a term on the blocks' sort column is a per-block binary search (also on the code stripe of a compressed sort column), a
       // term on a compressed attribute a scan of the code stripes with the comparison rewritten per block
-      if (t.id == kChar && b.compressedAttribute(term.attribute) == nullptr && term.attribute == b.sortColumn()) return false;
+      if (IsTextType(t.id) && b.compressedAttribute(term.attribute) == nullptr && term.attribute == b.sortColumn()) return false;
       if (reference_block == nullptr) reference_block = &b;
       const StorageBlock &f = *reference_block;
       if ((term.attribute == b.sortColumn()) != (term.attribute == f.sortColumn())) return false;
@@ -583,16 +595,26 @@ void SelectTermForRun(const std::vector<BlockReference> &blocks, const std::vect
     // the run's dictionaries — block b's code set —, one tests the code stripes for membership in their block's set
     std::vector<std::int64_t> dict_rows(nb, 0), num_codes(nb, 0);
     std::vector<const void *> dictionaries(nb, nullptr);
+    std::vector<const std::uint32_t *> offsets(nb, nullptr);   // a VARCHAR attribute: the variable-length dictionaries of the run
+    std::vector<std::int64_t> value_bytes(nb, 0);
     std::vector<std::uint64_t *> sets(nb, nullptr);
     std::size_t set_words = 0;
     int value_width = t.width;
+    const bool variable = t.id == kVarChar;
+    if (variable && !like) throw ExecutionError("IN list on a VARCHAR attribute", QSX_ERR_UNSUPPORTED);
     for (std::size_t b = 0; b < nb; ++b) {
       const CompressedAttribute *c = blocks[b]->compressedAttribute(term.attribute);
       stripes[b] = c != nullptr ? c->codes : nullptr;   // (nullptr: an empty block)
       if (c == nullptr) continue;
       dict_rows[b] = num_codes[b] = c->num_codes;
-      dictionaries[b] = c->dictionary;
-      value_width = c->value_width;
+      if (variable) {
+        dictionaries[b] = c->num_codes != 0 ? c->variable_values : nullptr;
+        offsets[b] = c->num_codes != 0 ? c->variable_offsets : nullptr;
+        value_bytes[b] = c->num_codes != 0 ? static_cast<std::int64_t>(c->variable_value_bytes) : 0;
+      } else {
+        dictionaries[b] = c->dictionary;
+        value_width = c->value_width;
+      }
       set_words += static_cast<std::size_t>((c->num_codes + 63) / 64) + 1;
     }
     scratch->emplace_back(new DeviceBuffer(set_words * 8 + 8));
@@ -601,7 +623,13 @@ void SelectTermForRun(const std::vector<BlockReference> &blocks, const std::vect
       sets[b] = static_cast<std::uint64_t *>(scratch->back()->ptr) + set_at;
       set_at += static_cast<std::size_t>((num_codes[b] + 63) / 64) + (num_codes[b] != 0 ? 1 : 0);
     }
-    if (like) {
+    if (variable) {
+      // every block's own variable-length dictionary, matched where the images hold them: one launch over the run
+      CheckStatus(qsx_select_like_var_blocks(t.width, static_cast<std::int64_t>(nb), dict_rows.data(), offsets.data(), dictionaries.data(),
+                                             value_bytes.data(), term.literal.text.data(), static_cast<int>(term.literal.text.size()),
+                                             term.comparison == ComparisonID::kNotLike ? 1 : 0, nullptr, sets.data(), nullptr, CurrentStream()),
+                  "qsx_select_like_var_blocks");
+    } else if (like) {
       CheckStatus(qsx_select_like_blocks(value_width, static_cast<std::int64_t>(nb), dict_rows.data(), dictionaries.data(), term.literal.text.data(),
                                          static_cast<int>(term.literal.text.size()), term.comparison == ComparisonID::kNotLike ? 1 : 0, nullptr,
                                          sets.data(), nullptr, CurrentStream()), "qsx_select_like_blocks");
@@ -640,7 +668,7 @@ void SelectTermForRun(const std::vector<BlockReference> &blocks, const std::vect
     CheckStatus(qsx_select_like_blocks(t.width, static_cast<std::int64_t>(nb), rows.data(), stripes.data(), term.literal.text.data(),
                                        static_cast<int>(term.literal.text.size()), term.comparison == ComparisonID::kNotLike ? 1 : 0, in_filters,
                                        outs, counts, CurrentStream()), "qsx_select_like_blocks");
-  } else if (t.id == kChar) {
+  } else if (IsTextType(t.id)) {
     // CHAR(n) OP string literal on plain stripes (AsciiStringUncheckedComparator, AsciiStringComparators.hpp:218-251)
     CheckStatus(qsx_select_cmp_char_blocks(t.width, static_cast<std::int64_t>(nb), rows.data(), stripes.data(), static_cast<int>(term.comparison),
                                            term.literal.text.data(), static_cast<int>(term.literal.text.size()), in_filters, outs, counts,
@@ -1326,8 +1354,12 @@ AggregationOperationState::AggregationOperationState(const AggregationStateSpec 
   // CHAR group-by attribute is presented as an INT column of ids out of a device dictionary of its values
   for (std::size_t k = 0; k < num_keys; ++k) {
     const Type &t = key_types[k];
-    const bool packs = t.width == 1 || t.width == 2 || t.width == 4 || t.width == 8;
-    if (t.id != kChar || (packs && config_.strategy != QSX_AGG_GENERIC) || internedKeyOf(config_.key_column[k]) >= 0) continue;
+    // (a VARCHAR(n) key is always interned: its stripe — decoded from the block's variable-length dictionary — holds CHAR(n) fields)
+    const bool packs = t.id == kChar && (t.width == 1 || t.width == 2 || t.width == 4 || t.width == 8);
+    if (!IsTextType(t.id) || (packs && config_.strategy != QSX_AGG_GENERIC) || internedKeyOf(config_.key_column[k]) >= 0) continue;
+    if (t.id == kVarChar && (t.width < 1 || t.width > QSX_MAX_CHAR_DICT_WIDTH)) {
+      throw ExecutionError("GROUP BY VARCHAR(n): n outside 1..QSX_MAX_CHAR_DICT_WIDTH", QSX_ERR_UNSUPPORTED);
+    }
     InternedKey key;
     key.column = config_.key_column[k];
     key.attribute = key_attributes[k];
@@ -1347,6 +1379,9 @@ AggregationOperationState::AggregationOperationState(const AggregationStateSpec 
       spec_.aggregates[a].argument_expression = nullptr;
     }
     const AggregateSpec &ag = spec_.aggregates[a];
+    if (ag.argument_expression == nullptr && ag.argument != kInvalidAttributeID && rel.getAttributeType(ag.argument).id == kVarChar) {
+      throw ExecutionError("a VARCHAR attribute as an aggregate's argument", QSX_ERR_UNSUPPORTED);
+    }
     if (ag.is_distinct && !unary_columns_.empty()) {   // (the distinctify tables are keyed by group-by ATTRIBUTES)
       throw ExecutionError("DISTINCT aggregate beside a unary group-by key", QSX_ERR_UNSUPPORTED);
     }
@@ -1498,7 +1533,9 @@ void AggregationOperationState::internBlocks(std::vector<InternRequest> *request
       r.ids[k] = ids;
       if (n == 0) continue;
       const CompressedAttribute *ca = key.derived ? nullptr : r.block->compressedAttribute(key.attribute);
-      if (!key.derived && ca != nullptr && ca->kind == CompressedAttribute::kDictionary && !r.block->valuesMaterialized(key.attribute)) {
+      // (a variable-length dictionary — a VARCHAR key — is no stripe of fixed fields: its block presents the decoded stripe)
+      if (!key.derived && ca != nullptr && ca->kind == CompressedAttribute::kDictionary && !ca->variable_length &&
+          !r.block->valuesMaterialized(key.attribute)) {
         // (one more entry than codes: the dictionary's NULL code, num_codes, maps to -1)
         coded.push_back(Coded{ca, n, static_cast<std::int32_t *>(scratch->take((static_cast<std::size_t>(ca->num_codes) + 1) * 4)), ids});
         continue;
@@ -1671,7 +1708,7 @@ void AggregationOperationState::aggregateBlock(const StorageBlock &block, const 
   for (std::size_t i = 0; i < column_attr_.size() && !any_nulls && case_columns_.empty() && unary_columns_.empty(); ++i) {
     const CompressedAttribute *ca = block.compressedAttribute(column_attr_[i]);
     const int type = config_.column_type[i];
-    if (ca != nullptr && type != kChar && internedKeyOf(i) < 0 && !block.valuesMaterialized(column_attr_[i])) {
+    if (ca != nullptr && type != kChar && !ca->variable_length && internedKeyOf(i) < 0 && !block.valuesMaterialized(column_attr_[i])) {
       code_width[i] = ca->code_width;
       any_coded = true;
     }
@@ -1871,7 +1908,8 @@ void AggregationOperationState::aggregateBlocks(const std::vector<BlockReference
       // null bitmaps travel with single-block calls (qsx_agg_update_nullable)
       if (block.nullBitmap(column_attr_[c]) != nullptr) in_run = false;
       const CompressedAttribute *ca = block.compressedAttribute(column_attr_[c]);
-      if (ca != nullptr && config_.column_type[c] != kChar && internedKeyOf(c) < 0 && !block.valuesMaterialized(column_attr_[c])) {
+      if (ca != nullptr && config_.column_type[c] != kChar && !ca->variable_length && internedKeyOf(c) < 0 &&
+          !block.valuesMaterialized(column_attr_[c])) {
         code_width[c] = ca->code_width;          // aggregated on its codes, like aggregateBlock does
         any_coded = true;
       }
@@ -2379,6 +2417,7 @@ QueryContext::join_hash_table_id QueryContext::addJoinHashTable(TypeID key_type,
                                                                 std::size_t num_partitions,
                                                                 const ExactKeyRange *exact_key_range) {
   std::vector<qsx_join_table_t *> parts(num_partitions, nullptr);
+  if (key_type == kVarChar) throw ExecutionError("a VARCHAR attribute as a join key", QSX_ERR_UNSUPPORTED);
   if (key_type == kChar) key_type = kLong;   // a CHAR(n <= 8) key travels as the LONG qsx_join_key_pack_char makes of it
   for (std::size_t p = 0; p < num_partitions; ++p) {
     if (exact_key_range != nullptr) {

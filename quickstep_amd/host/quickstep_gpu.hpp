@@ -83,6 +83,10 @@ struct Type {
   static Type Float() { return {kFloat, 4}; }
   static Type Double() { return {kDouble, 8}; }
   static Type Char(int n) { return {kChar, n}; }
+  // VARCHAR(n).  Outside the variable-length dictionary of an adopted compressed block (CompressedAttribute below) a value
+  // of this layer is an n-byte, NUL-padded field — CHAR(n)'s representation: the text ends at its first NUL or at n bytes.
+  // (A choice of this layer; the reference keeps such a column in a row store.  No value of a text without NULs changes.)
+  static Type VarChar(int n) { return {kVarChar, n}; }
   static Type Date() { return {kDate, 8}; }
   Type getNullableVersion() const { Type t = *this; t.nullable = true; return t; }
 };
@@ -153,16 +157,38 @@ struct PartitionedBlockIds {
 // How one attribute of a compressed column-store block is stored (CompressedBlockBuilder's choice,
 // storage/CompressedBlockBuilder.cpp:508-566, 590-650): a stripe of 1/2/4-byte unsigned codes that are the
 // values themselves (truncated non-negative INT/LONG) or indexes into a sorted dictionary.
+// The host side of a VARIABLE-LENGTH dictionary (a VARCHAR attribute): the offsets as adoption read and checked them, and
+// the value bytes, which only a comparison against a string literal needs (the binary search of the predicate rewriting) —
+// they are fetched by the first such comparison.  LIKE and decoding work on the device and never fetch them.
+struct VariableLengthDictionaryHost {
+  std::mutex mutex;
+  std::vector<std::uint32_t> offsets;   // num_codes, ascending, from the first value byte
+  bool values_fetched = false;
+  std::vector<unsigned char> values;
+};
 struct CompressedAttribute {
   enum Kind { kUncompressed = 0, kTruncated = 1, kDictionary = 2 };
   Kind kind = kUncompressed;
   int code_width = 0;
   std::uint32_t num_codes = 0;          // dictionary entries
   void *codes = nullptr;                // device: num_tuples codes
-  void *dictionary = nullptr;           // device copy of the dictionary (decode)
+  void *dictionary = nullptr;           // device copy of the dictionary (decode); nullptr for a variable-length one
   std::vector<unsigned char> dictionary_host;  // sorted values, attribute width each (predicate transformation)
   int value_width = 0;                  // CHAR(n) / DATE dictionaries: bytes per entry
+  // kDictionary of a VARCHAR attribute (compression/CompressionDictionaryLite.hpp:248-290): uint32 offset[num_codes], then
+  // the values back to back, each with its terminating NUL; entry c is [offset[c], offset[c + 1]), the last ends at
+  // variable_value_bytes.  The values are read where the image holds them; the offsets too, unless the image leaves them at
+  // an address that is no multiple of 4 — then variable_offsets is the block's own aligned copy (variable_offsets_owned).
+  bool variable_length = false;
+  const std::uint32_t *variable_offsets = nullptr;   // device
+  const void *variable_values = nullptr;             // device, any alignment
+  std::uint64_t variable_value_bytes = 0;
+  void *variable_offsets_owned = nullptr;
+  std::shared_ptr<VariableLengthDictionaryHost> variable_host;
 };
+// How often the value bytes of a variable-length dictionary were fetched to the host in this process (a comparison of a
+// VARCHAR attribute against a string literal does it once per block): what a test reads to see that LIKE and decoding do not.
+std::int64_t NumVariableDictionaryValueFetches();
 
 // Result of rewriting `attribute OP literal` into a comparison on codes
 // (CompressedAttributePredicateTransformer::TransformPredicateOnCompressedAttribute,
@@ -279,7 +305,8 @@ struct ReferenceBlockLayout {
 // Pure host logic: `prefix` = the first prefix_bytes of the image (the block header and the 8-byte sub-block header must lie
 // inside), image_bytes = its full size.  Throws ExecutionError(QSX_ERR_INVALID_ARGUMENT) for a malformed image
 // (StorageBlock.cpp:108-131 MalformedBlock) and QSX_ERR_UNSUPPORTED for a tuple store that is neither a basic nor a compressed
-// column store (row stores), or a compressed store with a variable-length attribute.
+// column store (row stores), or a basic column store of a relation with a VARCHAR attribute (a variable-length attribute lives
+// behind a dictionary: CompressedBlockBuilder.cpp:452-455; in a compressed store without one the image is malformed).
 ReferenceBlockLayout ParseReferenceBlockImage(const CatalogRelation &relation, const void *prefix, std::size_t prefix_bytes,
                                               std::size_t image_bytes);
 
@@ -332,7 +359,7 @@ struct TypedLiteral {
     std::memcpy(&l.v.i64, &d, 8);
     return l;
   }
-  // a string literal for a CHAR(n) attribute (compared like the reference's strcmpHelper: AsciiStringComparators.hpp:218-251)
+  // a string literal for a CHAR(n) or VARCHAR(n) attribute (compared like the reference's strcmpHelper: AsciiStringComparators.hpp:218-251)
   static TypedLiteral Char(const std::string &text) { TypedLiteral l; l.type = kChar; l.v.i64 = 0; l.text = text; return l; }
   std::string text;
 };

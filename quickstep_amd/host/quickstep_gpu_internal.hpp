@@ -155,12 +155,20 @@ inline std::unique_ptr<DeviceBuffer> CharKeyAsLong(const StorageBlock &block, at
   return out;
 }
 
+// VARCHAR is no join key of this layer (alone or as a component): refused before a key stripe is made of it.
+inline void RefuseVarCharJoinKey(const CatalogRelation &relation, const std::vector<attribute_id> &attrs) {
+  for (attribute_id a : attrs) {
+    if (relation.getAttributeType(a).id == kVarChar) throw ExecutionError("a VARCHAR attribute as a join key", QSX_ERR_UNSUPPORTED);
+  }
+}
+
 struct JoinKeys {
   const void *ptr = nullptr;
   bool exact = true;
   std::unique_ptr<DeviceBuffer> packed;
   std::vector<std::unique_ptr<DeviceBuffer>> char_keys;
   JoinKeys(const StorageBlock &block, const std::vector<attribute_id> &attrs) {
+    RefuseVarCharJoinKey(block.getRelation(), attrs);
     if (attrs.size() == 1) {
       if (block.getRelation().getAttributeType(attrs.front()).id == kChar) {
         char_keys.push_back(CharKeyAsLong(block, attrs.front()));
@@ -212,6 +220,7 @@ struct RunJoinKeys {
   const qsx_key_coding_t *coding() const { return coded ? &coding_ : nullptr; }
   RunJoinKeys(const std::vector<BlockReference> &blocks, const std::vector<attribute_id> &attrs, const std::vector<std::int64_t> &rows) {
     const CatalogRelation &relation = blocks.front()->getRelation();
+    RefuseVarCharJoinKey(relation, attrs);
     if (attrs.size() == 1) {
       const TypeID key_type = relation.getAttributeType(attrs.front()).id;
       for (const BlockReference &b : blocks) {
@@ -283,11 +292,14 @@ struct RunMatches {
   std::vector<std::uint64_t *> bitmaps;   // block b's bitmap under the whole conjunction
   std::vector<std::unique_ptr<DeviceBuffer>> scratch;   // code sets of LIKE terms on coded attributes: read by queued kernels
 };
-// LIKE / NOT LIKE terms (query_context.cpp).  CheckLikeTerm: QSX_ERR_UNSUPPORTED unless the term is CHAR(n) attribute against a
-// pattern literal of at most QSX_MAX_LIKE_PATTERN bytes.  SelectCharTerm: a CHAR(n) attribute against a string literal over a
+// LIKE / NOT LIKE terms (query_context.cpp).  CheckLikeTerm: QSX_ERR_UNSUPPORTED unless the term is CHAR(n) or VARCHAR(n)
+// attribute against a pattern literal of at most QSX_MAX_LIKE_PATTERN bytes.  SelectCharTerm: a CHAR(n) attribute against a string literal over a
 // plain stripe of n values — qsx_select_like for the two, qsx_select_cmp_char for the six orderings (whose ComparisonID is
 // the ABI's op).
 inline bool IsLikeComparison(ComparisonID c) { return c == ComparisonID::kLike || c == ComparisonID::kNotLike; }
+// CHAR(n) and VARCHAR(n): outside an adopted variable-length dictionary both are n-byte NUL-padded fields (Type::VarChar), so
+// a plain stripe of either goes through the CHAR(n) kernels.
+inline bool IsTextType(TypeID id) { return id == kChar || id == kVarChar; }
 void CheckLikeTerm(const ComparisonPredicate &term, const Type &type);
 // attribute OP attribute as a conjunct of a Select's, an aggregation's or a WHEN's predicate (query_context.cpp): throws unless both
 // attributes are `relation`'s own (no build side: QSX_ERR_INVALID_ARGUMENT), numeric with numeric or DATE with DATE, no LIKE

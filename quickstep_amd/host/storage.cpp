@@ -163,6 +163,7 @@ StorageBlock::~StorageBlock() {
   for (CompressedAttribute &c : compressed_) {
     qsx_device_free(c.codes);
     qsx_device_free(c.dictionary);
+    qsx_device_free(c.variable_offsets_owned);   // (the aligned copy of a variable-length dictionary's offsets, or nullptr)
   }
 }
 void StorageBlock::copyNullBitmapToHost(attribute_id a, std::uint64_t *dst) const {
@@ -198,7 +199,16 @@ void *StorageBlock::stripe(attribute_id a) const {
     const int width = relation_.getAttributeType(a).width;
     void *values = nullptr;
     CheckStatus(qsx_device_alloc(static_cast<std::size_t>(capacity_ ? capacity_ : 1) * width, &values), "qsx_device_alloc(decoded stripe)");
-    CheckStatus(qsx_decode_codes(c.code_width, c.codes, num_tuples_, c.dictionary, width, values, CurrentStream()), "qsx_decode_codes");
+    if (c.variable_length) {
+      // a VARCHAR(n) attribute: n-byte NUL-padded fields (CompressedTupleStorageSubBlock::getAttributeValue over a
+      // variable-length dictionary, per tuple in the reference); the NULL code gives an all-NUL field under the null bitmap
+      const int rc = qsx_decode_codes_var(c.code_width, c.codes, num_tuples_, c.variable_offsets, c.variable_values, c.num_codes,
+                                          static_cast<std::int64_t>(c.variable_value_bytes), width, values, CurrentStream());
+      if (rc != QSX_OK) qsx_device_free(values);
+      CheckStatus(rc, "qsx_decode_codes_var");
+    } else {
+      CheckStatus(qsx_decode_codes(c.code_width, c.codes, num_tuples_, c.dictionary, width, values, CurrentStream()), "qsx_decode_codes");
+    }
     CheckStatus(qsx_stream_synchronize(CurrentStream()), "qsx_stream_synchronize");   // other workers' streams read it next
     stripes_.at(a) = values;
   }
@@ -415,29 +425,11 @@ void BuildByteDictionary(TypeID type, int width, const unsigned char *values, st
   }
 }
 
-// The dictionary branch of TransformT for byte dictionaries (same rules: CompressedStoreUtil.cpp:425-616,
-// CompressionDictionary.cpp:276-305).
-PredicateTransformResult TransformBytes(const CompressedAttribute &attr, TypeID type, ComparisonID comparison, const void *literal,
-                                        std::size_t literal_length) {
+// What lower (first entry >= literal) and upper (first entry > literal) make of `code OP literal` over a sorted dictionary of
+// num_codes entries (CompressedStoreUtil.cpp:425-616, CompressionDictionary.cpp:276-305): shared by the fixed-width byte
+// dictionaries and the variable-length ones.
+PredicateTransformResult CodeComparisonFromBounds(ComparisonID comparison, std::uint32_t lower, std::uint32_t upper, std::uint32_t num_codes) {
   PredicateTransformResult r;
-  const int width = attr.value_width;
-  std::uint32_t lower = 0, upper = attr.num_codes;   // first entry >= literal, first entry > literal
-  {
-    std::uint32_t lo = 0, hi = attr.num_codes;
-    while (lo < hi) {
-      const std::uint32_t mid = lo + (hi - lo) / 2;
-      if (CompareBytesWithLiteral(type, attr.dictionary_host.data() + static_cast<std::size_t>(mid) * width, width, literal, literal_length) < 0) lo = mid + 1;
-      else hi = mid;
-    }
-    lower = lo;
-    hi = attr.num_codes;
-    while (lo < hi) {
-      const std::uint32_t mid = lo + (hi - lo) / 2;
-      if (CompareBytesWithLiteral(type, attr.dictionary_host.data() + static_cast<std::size_t>(mid) * width, width, literal, literal_length) <= 0) lo = mid + 1;
-      else hi = mid;
-    }
-    upper = lo;
-  }
   auto basic = [&](qsx_code_cmp_t comp, std::uint32_t code) {
     r.type = PredicateTransformResult::kBasicComparison;
     r.comp = comp;
@@ -457,11 +449,11 @@ PredicateTransformResult TransformBytes(const CompressedAttribute &attr, TypeID 
   switch (comparison) {
     case ComparisonID::kLess: range = {0, lower}; break;
     case ComparisonID::kLessOrEqual: range = {0, upper}; break;
-    case ComparisonID::kGreater: range = {upper, attr.num_codes}; break;
-    default: range = {lower, attr.num_codes}; break;
+    case ComparisonID::kGreater: range = {upper, num_codes}; break;
+    default: range = {lower, num_codes}; break;
   }
   if (range.first >= range.second) return r;
-  if (range.second == attr.num_codes) range.second = kMax;
+  if (range.second == num_codes) range.second = kMax;
   if (range.first == 0) {
     if (range.second == kMax) r.type = PredicateTransformResult::kAll;
     else basic(QSX_CODE_LT, range.second);
@@ -475,7 +467,73 @@ PredicateTransformResult TransformBytes(const CompressedAttribute &attr, TypeID 
   }
   return r;
 }
+
+// The dictionary branch of TransformT for byte dictionaries (same rules: CompressedStoreUtil.cpp:425-616,
+// CompressionDictionary.cpp:276-305).
+PredicateTransformResult TransformBytes(const CompressedAttribute &attr, TypeID type, ComparisonID comparison, const void *literal,
+                                        std::size_t literal_length) {
+  const int width = attr.value_width;
+  std::uint32_t lower = 0, upper = attr.num_codes;   // first entry >= literal, first entry > literal
+  {
+    std::uint32_t lo = 0, hi = attr.num_codes;
+    while (lo < hi) {
+      const std::uint32_t mid = lo + (hi - lo) / 2;
+      if (CompareBytesWithLiteral(type, attr.dictionary_host.data() + static_cast<std::size_t>(mid) * width, width, literal, literal_length) < 0) lo = mid + 1;
+      else hi = mid;
+    }
+    lower = lo;
+    hi = attr.num_codes;
+    while (lo < hi) {
+      const std::uint32_t mid = lo + (hi - lo) / 2;
+      if (CompareBytesWithLiteral(type, attr.dictionary_host.data() + static_cast<std::size_t>(mid) * width, width, literal, literal_length) <= 0) lo = mid + 1;
+      else hi = mid;
+    }
+    upper = lo;
+  }
+  return CodeComparisonFromBounds(comparison, lower, upper, attr.num_codes);
+}
+
+// The variable-length case (a VARCHAR attribute): the same search over entries of their own lengths, in the host copy of the
+// value bytes that the first comparison fetches (CompressedStoreUtil.cpp:51-140 searches the dictionary likewise:
+// CompressionDictionary::getLowerBoundCodeForUntypedValue over variableLengthGetUntypedValueHelper).  An entry carries its
+// terminating NUL; strcmpHelper stops there.
+std::atomic<std::int64_t> variable_value_fetches{0};
+PredicateTransformResult TransformVariableLength(const CompressedAttribute &attr, ComparisonID comparison, const void *literal,
+                                                 std::size_t literal_length) {
+  VariableLengthDictionaryHost &host = *attr.variable_host;
+  std::lock_guard<std::mutex> lock(host.mutex);
+  if (!host.values_fetched) {
+    host.values.resize(static_cast<std::size_t>(attr.variable_value_bytes));
+    if (!host.values.empty()) {
+      CheckStatus(qsx_copy_to_host(host.values.data(), attr.variable_values, host.values.size(), CurrentStream()),
+                  "qsx_copy_to_host(variable-length dictionary values)");
+    }
+    host.values_fetched = true;
+    ++variable_value_fetches;
+  }
+  const auto compare = [&](std::uint32_t code) {
+    const std::size_t begin = host.offsets[code], end = code + 1 < attr.num_codes ? host.offsets[code + 1] : host.values.size();
+    return CompareAsciiStrings(reinterpret_cast<const char *>(host.values.data()) + begin, end - begin, static_cast<const char *>(literal),
+                               literal_length);
+  };
+  std::uint32_t lo = 0, hi = attr.num_codes;
+  while (lo < hi) {   // first entry >= literal
+    const std::uint32_t mid = lo + (hi - lo) / 2;
+    if (compare(mid) < 0) lo = mid + 1;
+    else hi = mid;
+  }
+  const std::uint32_t lower = lo;
+  hi = attr.num_codes;
+  while (lo < hi) {   // first entry > literal
+    const std::uint32_t mid = lo + (hi - lo) / 2;
+    if (compare(mid) <= 0) lo = mid + 1;
+    else hi = mid;
+  }
+  return CodeComparisonFromBounds(comparison, lower, lo, attr.num_codes);
+}
 }  // namespace
+
+std::int64_t NumVariableDictionaryValueFetches() { return variable_value_fetches.load(); }
 
 PredicateTransformResult TransformPredicateOnCompressedAttribute(const CompressedAttribute &attribute, TypeID type,
                                                                  ComparisonID comparison, const TypedLiteral &literal) {
@@ -486,7 +544,12 @@ PredicateTransformResult TransformPredicateOnCompressedAttribute(const Compresse
     case kDouble: return TransformT<double>(attribute, comparison, literal.v.f64);
     case kDate: return TransformBytes(attribute, type, comparison, &literal.v.i64, 8);
     case kChar: return TransformBytes(attribute, type, comparison, literal.text.data(), literal.text.size());
-    default: throw ExecutionError("compressed attributes: INT / LONG / FLOAT / DOUBLE / DATE / CHAR(n)", QSX_ERR_UNSUPPORTED);
+    case kVarChar:
+      if (!attribute.variable_length || attribute.variable_host == nullptr) {
+        throw ExecutionError("a VARCHAR attribute is compressed behind a variable-length dictionary only", QSX_ERR_INVALID_ARGUMENT);
+      }
+      return TransformVariableLength(attribute, comparison, literal.text.data(), literal.text.size());
+    default: throw ExecutionError("compressed attributes: INT / LONG / FLOAT / DOUBLE / DATE / CHAR(n) / VARCHAR(n)", QSX_ERR_UNSUPPORTED);
   }
 }
 
@@ -508,8 +571,12 @@ void CompressValues(TypeID type, const void *values, std::int64_t n, CompressedA
 }
 
 void StorageBlock::compressAttribute(attribute_id a, const void *host_values) {
-  if (g_host_memory) return;   // CPU plumbing mode keeps plain stripes
   const Type &t = relation_.getAttributeType(a);
+  if (t.id == kVarChar) {
+    // (variable-length dictionaries are adopted from the reference's images, not built here)
+    throw ExecutionError("loadBlock: compressing a VARCHAR attribute (building a variable-length dictionary) is not supported", QSX_ERR_UNSUPPORTED);
+  }
+  if (g_host_memory) return;   // CPU plumbing mode keeps plain stripes
   if (compressed_.empty()) compressed_.resize(relation_.size());
   CompressedAttribute &c = compressed_.at(a);
   std::vector<unsigned char> codes_host;
@@ -745,6 +812,8 @@ ReferenceBlockLayout ParseReferenceBlockImage(const CatalogRelation &relation, c
       } else {
         out.dictionary_offset.push_back(static_cast<std::size_t>(-1));
         out.dictionary_bytes.push_back(0);
+        // "Variable-length types MUST use dictionary compression" (storage/CompressedBlockBuilder.cpp:452-455, 608-611)
+        if (t.id == kVarChar) Malformed("a VARCHAR attribute of a compressed column store without a dictionary");
         if (size != static_cast<std::size_t>(t.width)) {   // truncation: INT / LONG only, to 1 / 2 / 4 bytes (:319-337)
           if ((t.id != kInt && t.id != kLong) || (size != 1 && size != 2 && size != 4) || size >= static_cast<std::size_t>(t.width)) Malformed("truncated attribute");
         }
@@ -776,6 +845,10 @@ ReferenceBlockLayout ParseReferenceBlockImage(const CatalogRelation &relation, c
   std::size_t row_bytes = 0, nullable = 0;
   for (std::size_t a = 0; a < relation.size(); ++a) {
     const Type &t = relation.getAttributeType(static_cast<attribute_id>(a));
+    if (t.id == kVarChar) {   // (BasicColumnStoreTupleStorageSubBlock::DescriptionIsValid refuses variable-length attributes)
+      throw ExecutionError("block image: a VARCHAR attribute in a basic column store (a variable-length attribute is adopted behind "
+                           "the dictionary of a compressed column store only)", QSX_ERR_UNSUPPORTED);
+    }
     row_bytes += static_cast<std::size_t>(t.width);
     nullable += t.nullable ? 1 : 0;
   }
@@ -849,17 +922,61 @@ block_id StorageManager::adoptBlockImage(CatalogRelation *relation, void *image_
       // {uint32 num_codes; uint32 null_code; num_codes values in ascending order} (compression/CompressionDictionary.hpp:46-58)
       std::uint32_t head[2] = {0, 0};
       fetch(head, layout.dictionary_offset[a], 8);
-      const std::size_t value_bytes = static_cast<std::size_t>(head[0]) * static_cast<std::size_t>(t.width);
-      if (8 + value_bytes > layout.dictionary_bytes[a]) {
-        throw ExecutionError("malformed block image: dictionary shorter than its entry count (variable-length dictionaries are not adopted)",
-                             QSX_ERR_INVALID_ARGUMENT);
-      }
       c.kind = CompressedAttribute::kDictionary;
       c.num_codes = head[0];
-      c.dictionary = base + layout.dictionary_offset[a] + 8;
-      c.dictionary_host.resize(value_bytes);
-      if (value_bytes != 0) fetch(c.dictionary_host.data(), layout.dictionary_offset[a] + 8, value_bytes);
-      if (t.id == kChar || t.id == kDate) c.value_width = t.width;
+      if (t.id == kVarChar) {
+        // a variable-length dictionary (compression/CompressionDictionaryLite.hpp:248-290, CompressionDictionaryBuilder.cpp:53-66):
+        // uint32 offset[num_codes] from the first value byte, then the values back to back in code order, each with its
+        // terminating NUL (types/VarCharType.hpp:42,112); the last entry ends where the dictionary does.  The offsets
+        // (4 x num_codes bytes) are checked here from one copy; the value bytes stay where they are — their host copy is
+        // fetched by the first comparison that searches them (TransformVariableLength).
+        if (t.width < 1 || t.width > QSX_MAX_VARCHAR_LENGTH) {
+          throw ExecutionError("block image: VARCHAR(n) with n outside 1..QSX_MAX_VARCHAR_LENGTH", QSX_ERR_UNSUPPORTED);
+        }
+        const std::size_t offset_bytes = static_cast<std::size_t>(head[0]) * 4;
+        if (8 + offset_bytes > layout.dictionary_bytes[a]) Malformed("variable-length dictionary shorter than its offsets");
+        const std::size_t value_bytes = layout.dictionary_bytes[a] - 8 - offset_bytes;
+        if (value_bytes < head[0] || value_bytes > 0xFFFFFFFFull) Malformed("variable-length dictionary: fewer value bytes than entries");
+        c.variable_host = std::make_shared<VariableLengthDictionaryHost>();
+        std::vector<std::uint32_t> &offsets = c.variable_host->offsets;
+        offsets.resize(head[0]);
+        if (head[0] != 0) fetch(offsets.data(), layout.dictionary_offset[a] + 8, offset_bytes);
+        for (std::size_t e = 0; e < offsets.size(); ++e) {
+          const std::uint64_t end = e + 1 < offsets.size() ? offsets[e + 1] : value_bytes;
+          if (end <= offsets[e]) Malformed("variable-length dictionary: offsets that do not ascend inside the dictionary");
+          if (end - offsets[e] > static_cast<std::uint64_t>(t.width) + 1) Malformed("variable-length dictionary: an entry longer than VARCHAR(n) allows");
+        }
+        if (head[0] != 0) {
+          unsigned char last = 1;
+          fetch(&last, layout.dictionary_offset[a] + layout.dictionary_bytes[a] - 1, 1);
+          if (last != 0) Malformed("variable-length dictionary: the last value is not terminated");
+        }
+        c.variable_length = true;
+        c.variable_values = base + layout.dictionary_offset[a] + 8 + offset_bytes;
+        c.variable_value_bytes = value_bytes;
+        // (a dictionary without entries — an empty block, or one that holds NULLs only — has no offset array to point at)
+        c.variable_offsets = head[0] != 0 ? reinterpret_cast<const std::uint32_t *>(base + layout.dictionary_offset[a] + 8) : nullptr;
+        if ((reinterpret_cast<std::uintptr_t>(c.variable_offsets) & 3) != 0) {
+          // the dictionaries follow a protobuf of arbitrary length: the kernels read the offsets as words, so an aligned copy
+          // of the offsets (never of the values) is made
+          CheckStatus(qsx_device_alloc(offset_bytes, &c.variable_offsets_owned), "qsx_device_alloc(dictionary offsets)");
+          const int rc = qsx_copy_to_device(c.variable_offsets_owned, offsets.data(), offset_bytes, nullptr);
+          if (rc != QSX_OK || qsx_stream_synchronize(nullptr) != QSX_OK) {
+            qsx_device_free(c.variable_offsets_owned);
+            CheckStatus(rc != QSX_OK ? rc : QSX_ERR_HIP, "qsx_copy_to_device(dictionary offsets)");
+          }
+          c.variable_offsets = static_cast<const std::uint32_t *>(c.variable_offsets_owned);
+        }
+      } else {
+        const std::size_t value_bytes = static_cast<std::size_t>(head[0]) * static_cast<std::size_t>(t.width);
+        if (8 + value_bytes > layout.dictionary_bytes[a]) {
+          throw ExecutionError("malformed block image: dictionary shorter than its entry count", QSX_ERR_INVALID_ARGUMENT);
+        }
+        c.dictionary = base + layout.dictionary_offset[a] + 8;
+        c.dictionary_host.resize(value_bytes);
+        if (value_bytes != 0) fetch(c.dictionary_host.data(), layout.dictionary_offset[a] + 8, value_bytes);
+        if (t.id == kChar || t.id == kDate) c.value_width = t.width;
+      }
       if (head[1] != 0xFFFFFFFFu && layout.num_tuples > 0) {
         // a NULL is the code num_codes (CompressionDictionary.hpp:49-52, 114-115): the tuples that carry it become the
         // attribute's null bitmap, which every operator of this layer already honours — a predicate's match under a NULL
@@ -875,10 +992,12 @@ block_id StorageManager::adoptBlockImage(CatalogRelation *relation, void *image_
         qsx_device_free(count);
         if (rc != QSX_OK) {
           qsx_device_free(bitmap);
+          qsx_device_free(c.variable_offsets_owned);
           CheckStatus(rc, "qsx_select_codes(NULL code)");
         }
         if (!t.nullable) {
           qsx_device_free(bitmap);
+          qsx_device_free(c.variable_offsets_owned);
           throw ExecutionError("malformed block image: a NULL code in an attribute the relation declares NOT NULL", QSX_ERR_INVALID_ARGUMENT);
         }
         block->setNullBitmap(static_cast<attribute_id>(a), bitmap);

@@ -1088,6 +1088,63 @@ int qsx_eval_substring(const void *col_dev, int width, int64_t n, int start, int
 int qsx_eval_substring_blocks(int width, int64_t num_blocks, const int64_t *block_rows, const void *const *block_cols,
                               int start, int length, void *const *block_out, qsx_stream_t stream);
 
+/* K1 with a unary operation as the left operand: EXTRACT(YEAR FROM o_orderdate) = 1995, EXTRACT(MONTH FROM d) IN (..),
+ * SUBSTRING(c_phone FROM 1 FOR 2) IN ('13', '31', ..) (TPC-H Q22), SUBSTRING(x FROM 1 FOR 1) = '-'.  The reference's
+ * ComparisonPredicate takes any Scalar on its left: it evaluates the operand into a column vector
+ * (ScalarUnaryExpression::getAllValues, expressions/scalar/ScalarUnaryExpression.cpp:92-115, over the operators quoted at
+ * qsx_eval_date_extract / qsx_eval_substring) and compares that vector with the static value
+ * (expressions/predicate/ComparisonPredicate.cpp:209-240); an IN list is the disjunction of qsx_select_in.  Here the operand's
+ * value of a row exists in registers only: one pass over the stripe, one bit per row written — 8 bytes per date read instead of
+ * 8 read, 4 written and 4 read again.
+ *
+ * CONTRACT: every output word and every count equals, bit for bit, the composition of entry points above —
+ *   QSX_UNARY_DATE_FIELD  qsx_select_cmp(QSX_INT, ..) / qsx_select_in(QSX_INT, ..) over what qsx_eval_date_extract(unit, ..)
+ *                         writes.  col_dev: n dates, 8-byte aligned; width must be 8.  `literal` points to one int32, `literals`
+ *                         to num_literals int32 (literal_length / literal_lengths are not looked at).  Years are any int32.
+ *   QSX_UNARY_SUBSTRING   qsx_select_cmp_char / qsx_select_in_char at width m = min(width - start, length) over what
+ *                         qsx_eval_substring(col, width, n, start, length, ..) writes: the field ends at its first NUL, start >= len
+ *                         gives the empty string (a legal literal, which matches it), bytes >= 0x80 are compared as they are,
+ *                         both sides end at their first NUL or at their maximum length (strcmpHelper,
+ *                         AsciiStringComparators.hpp:218-251).  literal / literal_length as qsx_select_cmp_char, literals /
+ *                         literal_lengths as qsx_select_in_char (slots of QSX_MAX_CHAR_LITERAL bytes).
+ *   op        QSX_EQ .. QSX_GE.  There is no LIKE form: the host layer refuses LIKE / NOT LIKE over a unary operation.
+ *   filter, out_bitmap (fully overwritten, bits at positions >= n zero, also under negate), out_count (overwritten), the bit
+ *   order, n == 0, QSX_MAX_IN_LIST and negate are exactly qsx_select_in_char's.
+ * Errors are those of the composed calls.  QSX_ERR_INVALID_ARGUMENT: operand == NULL, n < 0, op outside QSX_EQ..QSX_GE, NULL
+ * pointers with n > 0, a NULL literal (dates; CHAR: with literal_length > 0), dates that are not 8-byte aligned or width != 8,
+ * width outside 1..255, start outside [0, width), length < 1, negative literal lengths, num_literals outside
+ * 1..QSX_MAX_IN_LIST, negate not 0 / 1.  QSX_ERR_UNSUPPORTED: a unit other than QSX_DATE_YEAR / QSX_DATE_MONTH, an operand kind
+ * other than the two below, a CHAR literal of more than QSX_MAX_CHAR_LITERAL bytes.  QSX_ERR_NO_DEVICE comes in front of every
+ * other check.  NULL operands are the caller's: AND-NOT the attribute's null bitmap (a comparison with a NULL is not true).
+ * Over a dictionary stripe (col_dev = the dictionary's values, n = num_codes) the result is that dictionary's code set for
+ * qsx_select_codes_in_set, as for qsx_select_like and qsx_select_in_char.
+ * The _blocks forms work on a run of blocks in one launch (arguments as qsx_select_cmp_char_blocks / qsx_select_in_char_blocks;
+ * one ScalarUnaryExpression::getAllValues and one comparison per SelectWorkOrder in the reference, SelectOperator.cpp:83-150):
+ * every block's bitmap and count are those of the single call on that block.
+ * QSX_ABI_VERSION did not change: a caller detects the capability by the presence of the symbols. */
+#define QSX_UNARY_DATE_FIELD 0
+#define QSX_UNARY_SUBSTRING 1
+typedef struct qsx_unary_operand {
+  int32_t kind;     /* QSX_UNARY_DATE_FIELD | QSX_UNARY_SUBSTRING */
+  int32_t unit;     /* DATE_FIELD: QSX_DATE_YEAR | QSX_DATE_MONTH */
+  int32_t start;    /* SUBSTRING: 0-based first byte, as qsx_eval_substring takes it */
+  int32_t length;   /* SUBSTRING: bytes, >= 1 */
+} qsx_unary_operand_t;
+int qsx_select_cmp_unary(const qsx_unary_operand_t *operand, const void *col_dev, int width, int64_t n, int op, const void *literal,
+                         int literal_length, const uint64_t *filter_dev, uint64_t *out_bitmap_dev, int64_t *out_count_dev,
+                         qsx_stream_t stream);
+int qsx_select_in_unary(const qsx_unary_operand_t *operand, const void *col_dev, int width, int64_t n, const void *literals,
+                        const int32_t *literal_lengths, int num_literals, int negate, const uint64_t *filter_dev,
+                        uint64_t *out_bitmap_dev, int64_t *out_count_dev, qsx_stream_t stream);
+int qsx_select_cmp_unary_blocks(const qsx_unary_operand_t *operand, int width, int64_t num_blocks, const int64_t *block_rows,
+                                const void *const *block_cols, int op, const void *literal, int literal_length,
+                                const uint64_t *const *block_filters, uint64_t *const *block_out_bitmaps, int64_t *out_counts_dev,
+                                qsx_stream_t stream);
+int qsx_select_in_unary_blocks(const qsx_unary_operand_t *operand, int width, int64_t num_blocks, const int64_t *block_rows,
+                               const void *const *block_cols, const void *literals, const int32_t *literal_lengths, int num_literals,
+                               int negate, const uint64_t *const *block_filters, uint64_t *const *block_out_bitmaps,
+                               int64_t *out_counts_dev, qsx_stream_t stream);
+
 typedef struct qsx_agg_config {
   int32_t strategy;                       /* qsx_agg_strategy_t */
   int32_t num_columns;                    /* columns handed to every qsx_agg_update */

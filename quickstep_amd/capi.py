@@ -143,6 +143,11 @@ _SIGNATURES = {
     "qsx_eval_date_extract_blocks": (_int, [_int, _i64, C.POINTER(_i64), _pp, _pp, _vp]),
     "qsx_eval_substring": (_int, [_vp, _int, _i64, _int, _int, _vp, _vp]),
     "qsx_eval_substring_blocks": (_int, [_int, _i64, C.POINTER(_i64), _pp, _int, _int, _pp, _vp]),
+    "qsx_select_cmp_unary": (_int, [C.POINTER(T.UnaryOperand), _vp, _int, _i64, _int, _vp, _int, _vp, _vp, _vp, _vp]),
+    "qsx_select_in_unary": (_int, [C.POINTER(T.UnaryOperand), _vp, _int, _i64, _vp, C.POINTER(_i32), _int, _int, _vp, _vp, _vp, _vp]),
+    "qsx_select_cmp_unary_blocks": (_int, [C.POINTER(T.UnaryOperand), _int, _i64, C.POINTER(_i64), _pp, _int, _vp, _int, _pp, _pp, _vp, _vp]),
+    "qsx_select_in_unary_blocks": (_int, [C.POINTER(T.UnaryOperand), _int, _i64, C.POINTER(_i64), _pp, _vp, C.POINTER(_i32), _int, _int, _pp, _pp,
+                                          _vp, _vp]),
     "qsx_agg_state_create": (_int, [C.POINTER(T.AggConfig), _pp]),
     "qsx_agg_state_destroy": (_int, [_vp]),
     "qsx_select_cmp_sorted_blocks": (_int, [_int, _i64, C.POINTER(_i64), _pp, _int, _vp, _pp, _pp, _vp, _vp]),
@@ -559,6 +564,90 @@ def eval_substring_blocks(cols, start, length, outs=None, stream=None):
     optr = (C.c_void_p * max(nb, 1))(*[o.data_ptr() if c.shape[0] else None for c, o in zip(cols, outs)])
     _check(_lib.qsx_eval_substring_blocks(width, nb, rows, cptr, int(start), int(length), optr, _stream(stream)), "qsx_eval_substring_blocks")
     return outs
+
+
+# ------------------------------------------------------------- predicates over a unary operation
+UNARY_DATE_TILE_ROWS = 512      # rows a wave of the date-field kernels takes at a time (csrc/unary_ops.hip kFieldTileRows)
+
+
+def unary_substring_tile_rows(width):
+    """Rows of the LDS tile of the substring predicate kernels on a CHAR(width) stripe (csrc/char_predicates.hpp char_tile_rows)."""
+    return min(1024, max(64, (48 * 1024 // width) // 64 * 64))
+
+
+def _unary_stripe(operand, col):
+    """-> (width, rows) of the stripe an operand reads: an int64 tensor of raw DateLit bytes, or uint8 of shape (n, width)."""
+    if operand.kind == T.UNARY_DATE_FIELD:
+        assert col.dtype == torch.int64
+        return 8, col.numel()
+    assert col.dtype == torch.uint8 and col.dim() == 2
+    return col.shape[1], col.shape[0]
+
+
+def _unary_literal(operand, literal):
+    """-> (buffer, length) of a comparison's literal: an int for a date field, a bytes object for a substring."""
+    if operand.kind == T.UNARY_DATE_FIELD:
+        return (C.c_int32 * 1)(literal), 0
+    return C.create_string_buffer(bytes(literal), max(len(literal), 1)), len(literal)
+
+
+def _unary_literals(operand, literals):
+    if operand.kind == T.UNARY_DATE_FIELD:
+        return (C.c_int32 * max(len(literals), 1))(*literals), None
+    return _in_char_literals(literals)
+
+
+def select_cmp_unary(operand, col, op, literal, filter_bitmap=None, stream=None, want_count=True, out_bitmap=None):
+    """K1 with a unary operation on the left: `EXTRACT(unit FROM col) op literal` (operand = T.date_field(unit), col an int64
+    tensor of raw DateLit bytes, literal an int) or `SUBSTRING(col, start, length) op literal` (operand = T.substring_of(start,
+    length), col a uint8 tensor of shape (n, width), literal a bytes object).  One pass, no intermediate column: (bitmap, count)."""
+    width, n = _unary_stripe(operand, col)
+    if out_bitmap is None:
+        out_bitmap = new_bitmap(n, col.device)
+    out_count = torch.zeros(1, dtype=torch.int64, device=col.device) if want_count else None
+    lit, length = _unary_literal(operand, literal)
+    _check(_lib.qsx_select_cmp_unary(C.byref(operand), _ptr(col), width, n, op, lit, length, _ptr(filter_bitmap), _ptr(out_bitmap),
+                                     _ptr(out_count), _stream(stream)), "qsx_select_cmp_unary")
+    return out_bitmap, out_count
+
+
+def select_in_unary(operand, col, literals, negate=False, filter_bitmap=None, stream=None, want_count=True, out_bitmap=None):
+    """The IN list (negate: NOT IN) over a unary operation, operands and stripes as select_cmp_unary; literals are ints for a date
+    field and bytes objects for a substring.  Over a dictionary stripe the bitmap is that dictionary's code set."""
+    width, n = _unary_stripe(operand, col)
+    if out_bitmap is None:
+        out_bitmap = new_bitmap(n, col.device)
+    out_count = torch.zeros(1, dtype=torch.int64, device=col.device) if want_count else None
+    slots, lengths = _unary_literals(operand, literals)
+    _check(_lib.qsx_select_in_unary(C.byref(operand), _ptr(col), width, n, slots, lengths, len(literals), int(negate), _ptr(filter_bitmap),
+                                    _ptr(out_bitmap), _ptr(out_count), _stream(stream)), "qsx_select_in_unary")
+    return out_bitmap, out_count
+
+
+def _unary_run(operand, cols, filters):
+    width = 8 if operand.kind == T.UNARY_DATE_FIELD else cols[0].shape[1]
+    nb, outs, counts, _, _, optr, fptr = _run_outputs([c if c.dim() == 1 else c[:, 0] for c in cols], filters)
+    rows = (C.c_int64 * max(nb, 1))(*[c.shape[0] for c in cols])
+    cptr = (C.c_void_p * max(nb, 1))(*[c.data_ptr() if c.numel() else None for c in cols])
+    return width, nb, outs, counts, rows, cptr, optr, fptr
+
+
+def select_cmp_unary_blocks(operand, cols, op, literal, filters=None, stream=None):
+    """select_cmp_unary over a run of blocks in one launch: (per-block bitmaps, counts int64[nb])."""
+    width, nb, outs, counts, rows, cptr, optr, fptr = _unary_run(operand, cols, filters)
+    lit, length = _unary_literal(operand, literal)
+    _check(_lib.qsx_select_cmp_unary_blocks(C.byref(operand), width, nb, rows, cptr, op, lit, length, fptr, optr, _ptr(counts),
+                                            _stream(stream)), "qsx_select_cmp_unary_blocks")
+    return outs, counts[:nb]
+
+
+def select_in_unary_blocks(operand, cols, literals, negate=False, filters=None, stream=None):
+    """select_in_unary over a run of blocks in one launch: (per-block bitmaps, counts int64[nb])."""
+    width, nb, outs, counts, rows, cptr, optr, fptr = _unary_run(operand, cols, filters)
+    slots, lengths = _unary_literals(operand, literals)
+    _check(_lib.qsx_select_in_unary_blocks(C.byref(operand), width, nb, rows, cptr, slots, lengths, len(literals), int(negate), fptr, optr,
+                                           _ptr(counts), _stream(stream)), "qsx_select_in_unary_blocks")
+    return outs, counts[:nb]
 
 
 def char_dict_hash(text, width):

@@ -19,6 +19,7 @@
 
 #include "common.hpp"
 #include "block_runs.hpp"
+#include "char_predicates.hpp"
 #include "scan.hpp"
 
 namespace qsx {
@@ -1109,10 +1110,7 @@ static int dispatch_select_runs(int op, const long long *runs_dev, long long til
 constexpr int kCharUnroll = 4;
 constexpr int kCharStripWords = 16 * 16 + 8;   // a wave's strip for one bitmap word of CHAR(16) rows, and the spare word
 constexpr size_t kCharDirectLds = static_cast<size_t>(kWavesPerBlock) * kCharUnroll * kCharStripWords * 4;
-struct CharLiteral {
-  unsigned char bytes[QSX_MAX_CHAR_LITERAL];
-  int length;   // bytes before the first NUL
-};
+// (CharLiteral: char_predicates.hpp)
 // All ones up to (not including) the first zero byte of x (byte 0 = the lowest), all ones when there is none.  (The classic
 // zero-byte test flags bytes ABOVE a zero byte by mistake now and then; its lowest flag is always a true one.)
 __device__ __forceinline__ unsigned long long up_to_first_zero_byte(unsigned long long x) {
@@ -1344,23 +1342,8 @@ __global__ __launch_bounds__(kBlock) void select_char_runs_kernel(const long lon
 // A numeric list is a predicate of the packed scan above (select_packed_group: 16 bytes per lane and load, the lanes of a
 // bitmap word merge their masks) with the literals as wave-uniform kernel arguments; a CHAR list is a test of
 // select_char_tile, which loads a row's bytes once and compares them with every literal.
+// The lists as the kernels hold them (InListPred, CharInList, CharInCompare) are in char_predicates.hpp.
 // ---------------------------------------------------------------------------
-template <typename T>
-struct InListPred {
-  T lits[QSX_MAX_IN_LIST];   // padded by the host to a multiple of four with copies of the first literal
-  int count;                 // multiple of 4
-  bool negate;
-  // Equality is the type's own ==: NaN is in no list, -0.0 equals 0.0 (LiteralComparators-inl.hpp:330-370 with EqualFunctor).
-  __device__ __forceinline__ bool operator()(T v) const {
-    bool any = false;
-#pragma unroll
-    for (int g = 0; g < QSX_MAX_IN_LIST; g += 4) {   // constant indices: the literals stay in scalar registers
-      if (g >= count) break;                         // wave-uniform
-      any = any || v == lits[g] || v == lits[g + 1] || v == lits[g + 2] || v == lits[g + 3];
-    }
-    return any != negate;
-  }
-};
 
 // A stripe whose start the packed kernel may not take (aligned16): a row per lane, the wave layout of select_cmp_kernel.
 template <typename T, int R>
@@ -1399,59 +1382,6 @@ __global__ __launch_bounds__(kBlock) void select_in_rows_kernel(const T *__restr
     if (threadIdx.x == 0 && block_count != 0) atomicAdd(out_count, block_count);
   }
 }
-
-// A CHAR list in device memory (staged alone, or behind the run table): read with wave-uniform indices.  Only the literals
-// that can equal a field of the stripe's width are kept (no longer than it), so on fields of width <= 16 every literal lies
-// in `first` / `second`.  The host pads the list to a multiple of four with copies of its first literal: the register path
-// fetches four literals at a time and compares without a branch.
-struct CharInList {
-  long long count, negate;                                              // count: a multiple of 4 (0: no literal can match)
-  long long wide;                                                       // some literal is longer than 8 bytes: `second` takes part
-  long long direct;                                                     // the host sized tiles and LDS for the register path (below)
-  unsigned long long first[QSX_MAX_IN_LIST], second[QSX_MAX_IN_LIST];   // bytes 0-7 / 8-15, big-endian, zero-padded
-  long long length[QSX_MAX_IN_LIST];                                    // bytes before the first NUL
-  unsigned char bytes[QSX_MAX_IN_LIST][QSX_MAX_CHAR_LITERAL];
-};
-static_assert(sizeof(CharInList) % 8 == 0, "lies in a table of 64-bit words");
-struct CharInCompare {
-  const CharInList *__restrict__ list;
-  struct Key16 {};
-  // The register path only where the host chose it for the whole launch (fields of width <= 16, EVERY stripe of the run on a
-  // 4-byte boundary): its tile size and its LDS strips are the host's to provide, so host and kernel must not decide apart.
-  __device__ __forceinline__ bool fits16() const { return list->direct != 0; }
-  __device__ __forceinline__ Key16 key16() const { return Key16{}; }
-  // strcmpHelper equality (AsciiStringComparators.hpp:218-251) of zero-padded texts: both 64-bit halves are the same.
-  // (`|` and `&`, not `||` and `&&`: one literal at a time behind a branch waited for a scalar load per comparison —
-  // 0.62 ms per 100 M CHAR(2) rows against 7 literals.)
-  __device__ __forceinline__ bool match16(const Key16 &, unsigned long long x_first, unsigned long long x_second) const {
-    bool any = false;
-    const int count = static_cast<int>(list->count);
-    if (list->wide != 0) {
-      for (int i = 0; i < count; i += 4) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) any |= (x_first == list->first[i + j]) & (x_second == list->second[i + j]);
-      }
-    } else {   // no literal reaches the second half: the text must end inside the first
-      for (int i = 0; i < count; i += 4) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) any |= x_first == list->first[i + j];
-      }
-      any &= x_second == 0ull;
-    }
-    return any != (list->negate != 0);
-  }
-  __device__ __forceinline__ bool match(const unsigned char *v, int width) const {
-    bool any = false;
-    const int count = static_cast<int>(list->count);
-    for (int i = 0; i < count && !any; ++i) {
-      const int len = static_cast<int>(list->length[i]);          // <= width
-      bool same = len == width || v[len] == 0;                    // the text ends where the literal does
-      for (int j = 0; j < len && same; ++j) same = v[j] == list->bytes[i][j];
-      any = same;
-    }
-    return any != (list->negate != 0);
-  }
-};
 
 __global__ __launch_bounds__(kBlock) void select_in_char_kernel(const unsigned char *__restrict__ col, int width, int64_t n,
                                                                const CharInList *__restrict__ list, const uint64_t *__restrict__ filter,
@@ -1640,15 +1570,6 @@ static int sorted_runs(int64_t num_blocks, const int64_t *block_rows, const void
 
 // ---- IN lists: host side ---------------------------------------------------------------------------------------------------
 template <typename T>
-static InListPred<T> in_list_pred(const void *literals, int num_literals, int negate) {
-  InListPred<T> pred{};
-  std::memcpy(pred.lits, literals, sizeof(T) * static_cast<size_t>(num_literals));
-  pred.count = (num_literals + 3) / 4 * 4;
-  for (int i = num_literals; i < pred.count; ++i) pred.lits[i] = pred.lits[0];   // duplicates change nothing
-  pred.negate = negate != 0;
-  return pred;
-}
-template <typename T>
 static int launch_select_in(const void *col, int64_t n, const void *literals, int num_literals, int negate, const uint64_t *filter,
                             uint64_t *out, int64_t *out_count, hipStream_t stream) {
   const InListPred<T> pred = in_list_pred<T>(literals, num_literals, negate);
@@ -1670,42 +1591,7 @@ static int launch_select_in_runs(const long long *runs_dev, long long tiles, con
   QSX_CHECK_LAUNCH();
   return QSX_OK;
 }
-// The list as the CHAR kernels read it, or QSX_ERR_UNSUPPORTED for a literal of more than QSX_MAX_CHAR_LITERAL bytes.
-static int char_in_list(int width, const void *literals, const int32_t *literal_lengths, int num_literals, int negate, CharInList *list) {
-  std::memset(list, 0, sizeof(CharInList));
-  list->negate = negate;
-  for (int k = 0; k < num_literals; ++k) {
-    if (literal_lengths[k] < 0) return QSX_ERR_INVALID_ARGUMENT;
-    if (literal_lengths[k] > QSX_MAX_CHAR_LITERAL) return QSX_ERR_UNSUPPORTED;
-  }
-  for (int k = 0; k < num_literals; ++k) {
-    const unsigned char *text = static_cast<const unsigned char *>(literals) + static_cast<size_t>(k) * QSX_MAX_CHAR_LITERAL;
-    int len = 0;
-    while (len < literal_lengths[k] && text[len] != 0) ++len;   // a NUL ends it
-    if (len > width) continue;                                  // equals no field of this width
-    const long long at = list->count++;
-    list->length[at] = len;
-    if (len > 8) list->wide = 1;
-    for (int i = 0; i < len; ++i) {
-      list->bytes[at][i] = text[i];
-      if (i < 8) list->first[at] |= static_cast<unsigned long long>(text[i]) << (8 * (7 - i));
-      else if (i < 16) list->second[at] |= static_cast<unsigned long long>(text[i]) << (8 * (15 - i));
-    }
-  }
-  for (; list->count % 4 != 0; ++list->count) {   // a multiple of four, by copies of the first literal: duplicates change nothing
-    list->first[list->count] = list->first[0];
-    list->second[list->count] = list->second[0];
-    list->length[list->count] = list->length[0];
-    std::memcpy(list->bytes[list->count], list->bytes[0], QSX_MAX_CHAR_LITERAL);
-  }
-  return QSX_OK;
-}
-static int char_tile_rows(int width) {   // as qsx_select_cmp_char: a multiple of 64 (whole bitmap words), at most 48 KiB of LDS
-  int tile_rows = (48 * 1024 / width) / 64 * 64;
-  if (tile_rows > 1024) tile_rows = 1024;
-  if (tile_rows < 64) tile_rows = 64;
-  return tile_rows;
-}
+// (char_in_list, char_tile_rows: char_predicates.hpp)
 
 extern "C" {
 
@@ -1720,12 +1606,7 @@ int qsx_select_cmp_char(const void *col_dev, int width, int64_t n, int op, const
   hipStream_t s = as_stream(stream);
   if (out_count_dev != nullptr) QSX_HIP_TRY(hipMemsetAsync(out_count_dev, 0, sizeof(int64_t), s));
   if (n == 0) return QSX_OK;
-  CharLiteral lit{};
-  lit.length = 0;
-  while (lit.length < literal_length && static_cast<const unsigned char *>(literal)[lit.length] != 0) {   // a NUL ends it
-    lit.bytes[lit.length] = static_cast<const unsigned char *>(literal)[lit.length];
-    ++lit.length;
-  }
+  const CharLiteral lit = char_literal(literal, literal_length);
   // rows per tile: a multiple of 64 (whole bitmap words), at most 48 KiB of LDS
   int tile_rows = (48 * 1024 / width) / 64 * 64;
   if (tile_rows > 1024) tile_rows = 1024;
@@ -1755,12 +1636,7 @@ int qsx_select_cmp_char_blocks(int width, int64_t num_blocks, const int64_t *blo
   if (!run_blocks_ok(num_blocks, block_rows, block_cols, reinterpret_cast<const void *const *>(block_out_bitmaps))) return QSX_ERR_INVALID_ARGUMENT;
   hipStream_t s = as_stream(stream);
   if (out_counts_dev != nullptr) QSX_HIP_TRY(hipMemsetAsync(out_counts_dev, 0, sizeof(int64_t) * static_cast<size_t>(num_blocks), s));
-  CharLiteral lit{};
-  lit.length = 0;
-  while (lit.length < literal_length && static_cast<const unsigned char *>(literal)[lit.length] != 0) {   // a NUL ends it
-    lit.bytes[lit.length] = static_cast<const unsigned char *>(literal)[lit.length];
-    ++lit.length;
-  }
+  const CharLiteral lit = char_literal(literal, literal_length);
   int tile_rows = (48 * 1024 / width) / 64 * 64;   // as qsx_select_cmp_char
   if (tile_rows > 1024) tile_rows = 1024;
   if (tile_rows < 64) tile_rows = 64;

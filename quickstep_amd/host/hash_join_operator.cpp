@@ -51,6 +51,15 @@ bool HashJoinOperator::getAllWorkOrders(WorkOrdersContainer *container, QueryCon
     throw ExecutionError("HashJoinOperator: a residual predicate with a tree (OR / NOT / IN); only a conjunction of comparisons",
                          QSX_ERR_UNSUPPORTED);
   }
+  if (residual != nullptr) {
+    for (const ComparisonPredicate &term : residual->conjuncts) {
+      // the residual compares attributes of gathered pairs: there is no stripe for a unary operation to pass over
+      if (term.operand != nullptr) {
+        throw ExecutionError("HashJoinOperator: a residual predicate term with a scalar operand (EXTRACT / SUBSTRING); only attributes and literals",
+                             QSX_ERR_UNSUPPORTED);
+      }
+    }
+  }
   std::lock_guard<std::mutex> lock(mutex_);
   if (!started_) {
     // the build operator is a blocking dependency: it has published its key attributes by now

@@ -54,6 +54,83 @@ PredicateNodePtr Predicate::And(std::vector<PredicateNodePtr> children) { return
 PredicateNodePtr Predicate::Or(std::vector<PredicateNodePtr> children) { return NodeOver(PredicateNode::kDisjunction, std::move(children)); }
 PredicateNodePtr Predicate::Not(PredicateNodePtr child) { return NodeOver(PredicateNode::kNegation, {std::move(child)}); }
 
+PredicateNodePtr Predicate::In(ScalarPtr operand, std::vector<TypedLiteral> literals) {
+  auto n = std::make_shared<PredicateNode>();
+  n->kind = PredicateNode::kInList;
+  n->comparison = ComparisonPredicate::OnScalar(std::move(operand), ComparisonID::kEqual, TypedLiteral::Long(0));   // (the literals: in_literals)
+  n->in_literals = std::move(literals);
+  return n;
+}
+
+// ---------------------------------------------------------------------------
+// Terms over a unary operation (ComparisonPredicate::operand)
+// ---------------------------------------------------------------------------
+ComparisonPredicate ComparisonPredicate::OnScalar(ScalarPtr scalar, ComparisonID c, TypedLiteral l) {
+  // `attribute`: the operation's attribute, whose null bitmap is the term's (kInvalidAttributeID for a scalar CheckUnaryTerm refuses)
+  const bool unary_of_attribute = scalar != nullptr && scalar->kind == Scalar::kUnaryExpression && scalar->operand != nullptr &&
+                                  scalar->operand->kind == Scalar::kAttribute;
+  ComparisonPredicate p(unary_of_attribute ? scalar->operand->attribute : kInvalidAttributeID, c, std::move(l));
+  p.operand = std::move(scalar);
+  return p;
+}
+
+// The operand of such a term: a unary operation of an attribute (no VARCHAR), no LIKE, no second attribute.  Returns the
+// operand's type — INT, or CHAR(m) — which the literal(s) must have (CheckUnaryLiteral).
+Type CheckUnaryTerm(const ComparisonPredicate &term, const CatalogRelation &relation) {
+  const ScalarPtr &s = term.operand;
+  if (term.rhs_attribute != kInvalidAttributeID) {
+    throw ExecutionError("a predicate term with a scalar operand and rhs_attribute: the right side of a unary operation is a literal", QSX_ERR_INVALID_ARGUMENT);
+  }
+  if (s == nullptr || s->kind != Scalar::kUnaryExpression || s->operand == nullptr || s->operand->kind != Scalar::kAttribute) {
+    throw ExecutionError("a predicate term's scalar operand that is not EXTRACT / SUBSTRING of an attribute", QSX_ERR_UNSUPPORTED);
+  }
+  if (IsLikeComparison(term.comparison)) throw ExecutionError("LIKE / NOT LIKE over a unary operation (EXTRACT / SUBSTRING)", QSX_ERR_UNSUPPORTED);
+  if (relation.getAttributeType(s->operand->attribute).id == kVarChar) {
+    throw ExecutionError("a predicate term over a unary operation of a VARCHAR attribute", QSX_ERR_UNSUPPORTED);
+  }
+  return UnaryResultType(s, relation);   // (the operation's own rules: a DATE / a CHAR(n) attribute, the unit, the window)
+}
+void CheckUnaryLiteral(const Type &operand_type, const TypedLiteral &literal) {
+  if (literal.type != operand_type.id) {
+    throw ExecutionError("a predicate term over a unary operation: EXTRACT wants an INT literal, SUBSTRING a CHAR literal", QSX_ERR_UNSUPPORTED);
+  }
+  if (operand_type.id == kChar && literal.text.size() > QSX_MAX_CHAR_LITERAL) {
+    throw ExecutionError("a CHAR literal longer than QSX_MAX_CHAR_LITERAL bytes", QSX_ERR_UNSUPPORTED);
+  }
+}
+static bool SameOperand(const ScalarPtr &a, const ScalarPtr &b) {
+  if (a == nullptr || b == nullptr) return a == b;
+  if (a == b) return true;
+  if (a->kind != Scalar::kUnaryExpression || b->kind != Scalar::kUnaryExpression || a->unary_operation != b->unary_operation) return false;
+  if (a->operand == nullptr || b->operand == nullptr || a->operand->kind != Scalar::kAttribute || b->operand->kind != Scalar::kAttribute ||
+      a->operand->attribute != b->operand->attribute) {
+    return false;
+  }
+  return a->unary_operation == UnaryOperationID::kDateExtract ? a->date_extract_unit == b->date_extract_unit
+                                                              : a->substring_start == b->substring_start && a->substring_length == b->substring_length;
+}
+static qsx_unary_operand_t UnaryOperandOf(const Scalar &s) {
+  qsx_unary_operand_t operand = {};
+  if (s.unary_operation == UnaryOperationID::kDateExtract) {
+    operand.kind = QSX_UNARY_DATE_FIELD;
+    operand.unit = s.date_extract_unit;
+  } else {
+    operand.kind = QSX_UNARY_SUBSTRING;
+    operand.start = s.substring_start;
+    operand.length = s.substring_length;
+  }
+  return operand;
+}
+// The stripe width the entry points take for an attribute of type t: 8 for a date, n for CHAR(n).
+static int UnaryStripeWidth(const Type &t) { return t.id == kDate ? 8 : t.width; }
+// May the term be evaluated over block's dictionary of attribute a (its result: the code set)?  A fixed-width dictionary; a
+// dictionary of dates inside an adopted image may lie anywhere, and the date kernels want 8-byte alignment.
+static bool UnaryOnDictionary(const StorageBlock &block, attribute_id a, const Type &t) {
+  const CompressedAttribute *c = block.compressedAttribute(a);
+  return c != nullptr && c->kind == CompressedAttribute::kDictionary && !c->variable_length && c->num_codes > 0 &&
+         (t.id != kDate || (reinterpret_cast<std::uintptr_t>(c->dictionary) & 7) == 0);
+}
+
 // attribute OP attribute outside a join residual: both attributes are the input relation's, numeric with numeric or DATE with DATE
 void CheckAttributeComparison(const ComparisonPredicate &term, const CatalogRelation &relation) {
   if (term.on_build_side || term.rhs_on_build_side) {
@@ -69,6 +146,7 @@ void CheckAttributeComparison(const ComparisonPredicate &term, const CatalogRela
 namespace {
 std::atomic<std::int64_t> tree_block_evaluations{0}, tree_run_evaluations{0};
 std::atomic<std::int64_t> attribute_comparison_block_evaluations{0}, attribute_comparison_run_evaluations{0};
+std::atomic<std::int64_t> unary_block_evaluations{0}, unary_run_evaluations{0};
 
 // One side of `attribute OP attribute` over nb blocks as the blocks hold it (qsx_operand_coding_t): values, or the codes of a
 // compressed attribute with the block's code width, dictionary and number of codes — nothing is decoded.
@@ -181,7 +259,7 @@ class TreeCompiler {
     for (std::size_t k = 0; k < out_->leaves.size(); ++k) {
       const TreeLeaf &l = out_->leaves[k];
       if (l.null_of == kInvalidAttributeID && l.in == nullptr && l.term.attribute == term.attribute && l.term.comparison == term.comparison &&
-          SameLiteral(l.term.literal, term.literal)) {
+          SameLiteral(l.term.literal, term.literal) && SameOperand(l.term.operand, term.operand)) {
         return static_cast<int>(k);
       }
     }
@@ -190,18 +268,21 @@ class TreeCompiler {
     out_->leaves.push_back(leaf);
     return static_cast<int>(out_->leaves.size() - 1);
   }
-  int inLeaf(const PredicateNode &node, std::size_t begin, std::size_t end) {
+  int inLeaf(const PredicateNode &node, const Type &operand_type, std::size_t begin, std::size_t end) {
     for (std::size_t k = 0; k < out_->leaves.size(); ++k) {
       const TreeLeaf &l = out_->leaves[k];
-      // the same attribute against the same literals in the same order, wherever in the tree the list was written
-      if (l.in == nullptr || l.term.attribute != node.comparison.attribute || l.in_end - l.in_begin != end - begin) continue;
+      // the same operand against the same literals in the same order, wherever in the tree the list was written
+      if (l.in == nullptr || l.term.attribute != node.comparison.attribute || !SameOperand(l.term.operand, node.comparison.operand) ||
+          l.in_end - l.in_begin != end - begin) {
+        continue;
+      }
       bool same = true;
       for (std::size_t i = 0; i < end - begin && same; ++i) same = SameLiteral((*l.in_source)[l.in_begin + i], node.in_literals[begin + i]);
       if (same) return static_cast<int>(k);
     }
     TreeLeaf leaf;
     leaf.term = node.comparison;
-    leaf.in = std::make_shared<InListLiterals>(MakeInList(relation_.getAttributeType(node.comparison.attribute), node.in_literals, begin, end));
+    leaf.in = std::make_shared<InListLiterals>(MakeInList(operand_type, node.in_literals, begin, end));
     leaf.in_source = &node.in_literals;
     leaf.in_begin = begin;
     leaf.in_end = end;
@@ -227,6 +308,7 @@ class TreeCompiler {
   void walk(const PredicateNode &node) {
     switch (node.kind) {
       case PredicateNode::kComparison: {
+        if (node.comparison.operand != nullptr) CheckUnaryLiteral(CheckUnaryTerm(node.comparison, relation_), node.comparison.literal);
         if (node.comparison.rhs_attribute != kInvalidAttributeID) {
           throw ExecutionError("predicate tree: a comparison of two attributes as a leaf", QSX_ERR_UNSUPPORTED);
         }
@@ -236,19 +318,26 @@ class TreeCompiler {
       }
       case PredicateNode::kInList: {
         // InValueList::concretize (InValueList.cpp:40-65): a disjunction of equalities
+        const bool unary = node.comparison.operand != nullptr;
+        // the operand's type: the attribute's, or the unary operation's result (an INT, a CHAR(m))
+        const Type t = unary ? CheckUnaryTerm(node.comparison, relation_) : relation_.getAttributeType(node.comparison.attribute);
         const attribute_id a = node.comparison.attribute;
-        const Type &t = relation_.getAttributeType(a);
         if (node.in_literals.empty()) throw ExecutionError("IN list without a literal", QSX_ERR_INVALID_ARGUMENT);
         if (t.id == kVarChar) throw ExecutionError("IN list on a VARCHAR attribute", QSX_ERR_UNSUPPORTED);
+        if (unary) {
+          for (const TypedLiteral &l : node.in_literals) CheckUnaryLiteral(t, l);
+        }
         if (expand_in_(a)) {
           for (std::size_t k = 0; k < node.in_literals.size(); ++k) {
             if (node.in_literals[k].type != t.id) throw ExecutionError("IN list: a literal whose type differs from the operand's", QSX_ERR_UNSUPPORTED);
-            push(termLeaf(ComparisonPredicate(a, ComparisonID::kEqual, node.in_literals[k])));
+            ComparisonPredicate equality(a, ComparisonID::kEqual, node.in_literals[k]);
+            equality.operand = node.comparison.operand;
+            push(termLeaf(equality));
             if (k > 0) push(QSX_BOOL_OR);
           }
         } else {   // more than QSX_MAX_IN_LIST literals: several IN leaves under an OR
           for (std::size_t begin = 0; begin < node.in_literals.size(); begin += QSX_MAX_IN_LIST) {
-            push(inLeaf(node, begin, std::min(node.in_literals.size(), begin + QSX_MAX_IN_LIST)));
+            push(inLeaf(node, t, begin, std::min(node.in_literals.size(), begin + QSX_MAX_IN_LIST)));
             if (begin > 0) push(QSX_BOOL_OR);
           }
         }
@@ -298,6 +387,24 @@ void SelectInList(const InListLiterals &in, const Type &t, const void *stripe, i
   }
 }
 
+// A term over a unary operation against a stripe of the operation's attribute (a column stripe, or a dictionary: then the result
+// is that dictionary's code set).  in != nullptr: the IN list.
+void SelectUnaryTerm(const ComparisonPredicate &term, const Type &operand_type, const InListLiterals *in, const void *stripe, int width,
+                     std::int64_t n, const std::uint64_t *filter, std::uint64_t *out_bitmap, std::int64_t *out_count) {
+  const qsx_unary_operand_t operand = UnaryOperandOf(*term.operand);
+  const bool text = operand_type.id == kChar;
+  if (in != nullptr) {
+    CheckStatus(qsx_select_in_unary(&operand, stripe, width, n, text ? static_cast<const void *>(in->slots.data()) : in->values.data(),
+                                    text ? in->lengths.data() : nullptr, in->count, 0, filter, out_bitmap, out_count, CurrentStream()),
+                "qsx_select_in_unary");
+  } else {
+    CheckStatus(qsx_select_cmp_unary(&operand, stripe, width, n, static_cast<int>(term.comparison),
+                                     text ? static_cast<const void *>(term.literal.text.data()) : &term.literal.v.i32,
+                                     text ? static_cast<int>(term.literal.text.size()) : 0, filter, out_bitmap, out_count, CurrentStream()),
+                "qsx_select_cmp_unary");
+  }
+}
+
 // ONE term over ONE block into a bitmap — the place both the conjunction chain and the leaves of a tree go through: plain
 // stripes, CHAR(n), LIKE, compressed attributes with the comparison rewritten on the block's codes, the search on the sort
 // column, and the code set of a LIKE or an IN list against the block's dictionary.  in != nullptr: `term.attribute IN (..)`.
@@ -305,11 +412,31 @@ void SelectInList(const InListLiterals &in, const Type &t, const void *stripe, i
 void SelectTermForBlock(const StorageBlock &block, const ComparisonPredicate &term, const InListLiterals *in, const std::uint64_t *filter,
                         std::uint64_t *out_bitmap, std::int64_t *out_count, TermScratch *scratch) {
   const std::int64_t n = block.numTuples();
-  if (in == nullptr && term.rhs_attribute != kInvalidAttributeID) {
+  if (in == nullptr && term.operand == nullptr && term.rhs_attribute != kInvalidAttributeID) {
     // attribute OP attribute (ComparisonPredicate.cpp:243-333): both sides as the block holds them, the run form with one block
     const StorageBlock *one = &block;
     SelectAttributeComparison(&one, 1, &n, term, filter != nullptr ? &filter : nullptr, &out_bitmap, out_count);
     ++attribute_comparison_block_evaluations;
+    return;
+  }
+  if (term.operand != nullptr) {
+    // a unary operation of the attribute on the left (ComparisonPredicate.cpp:209-240 over ScalarUnaryExpression::getAllValues):
+    // one pass over the stripe, or over the block's dictionary (the term's code set) and then the code stripe; any other
+    // compressed form is read as the decoded stripe
+    const Type operand_type = CheckUnaryTerm(term, block.getRelation());
+    if (in == nullptr) CheckUnaryLiteral(operand_type, term.literal);
+    const Type &attribute_type = block.getRelation().getAttributeType(term.attribute);
+    if (UnaryOnDictionary(block, term.attribute, attribute_type)) {
+      const CompressedAttribute *dict = block.compressedAttribute(term.attribute);
+      scratch->emplace_back(new DeviceBuffer(static_cast<std::size_t>((dict->num_codes + 63) / 64) * 8 + 8));
+      std::uint64_t *set = static_cast<std::uint64_t *>(scratch->back()->ptr);
+      SelectUnaryTerm(term, operand_type, in, dict->dictionary, attribute_type.id == kDate ? 8 : dict->value_width, dict->num_codes, nullptr, set, nullptr);
+      CheckStatus(qsx_select_codes_in_set(dict->code_width, dict->codes, n, set, dict->num_codes, filter, out_bitmap, out_count, CurrentStream()),
+                  "qsx_select_codes_in_set");
+    } else {
+      SelectUnaryTerm(term, operand_type, in, block.stripe(term.attribute), UnaryStripeWidth(attribute_type), n, filter, out_bitmap, out_count);
+    }
+    ++unary_block_evaluations;
     return;
   }
   const Type &t = block.getRelation().getAttributeType(term.attribute);
@@ -403,6 +530,8 @@ std::int64_t NumPredicateTreeBlockEvaluations() { return tree_block_evaluations.
 std::int64_t NumPredicateTreeRunEvaluations() { return tree_run_evaluations.load(); }
 std::int64_t NumAttributeComparisonBlockEvaluations() { return attribute_comparison_block_evaluations.load(); }
 std::int64_t NumAttributeComparisonRunEvaluations() { return attribute_comparison_run_evaluations.load(); }
+std::int64_t NumUnaryPredicateBlockEvaluations() { return unary_block_evaluations.load(); }
+std::int64_t NumUnaryPredicateRunEvaluations() { return unary_run_evaluations.load(); }
 
 void LowerPredicateToAggConfig(const Predicate &predicate, const CatalogRelation &relation, const std::function<int(attribute_id)> &column_of,
                                qsx_agg_config_t *config, Predicate *external) {
@@ -411,6 +540,13 @@ void LowerPredicateToAggConfig(const Predicate &predicate, const CatalogRelation
   };
   int in_state = 0;
   for (const ComparisonPredicate &term : predicate.conjuncts) {
+    if (term.operand != nullptr) {
+      // qsx_agg_config_t.pred names a column: a term over a unary operation is the external predicate's
+      CheckUnaryLiteral(CheckUnaryTerm(term, relation), term.literal);
+      keep_out("a term over a unary operation (EXTRACT / SUBSTRING)");
+      external->conjuncts.push_back(term);
+      continue;
+    }
     const Type &t = relation.getAttributeType(term.attribute);
     if (IsLikeComparison(term.comparison)) CheckLikeTerm(term, t);   // (a CHAR(n) term: evaluated by Predicate)
     if (IsTextType(t.id) || term.rhs_attribute != kInvalidAttributeID || in_state == QSX_MAX_PRED_TERMS) {
@@ -507,6 +643,18 @@ bool RunPredicateCovers(const Predicate &predicate, const std::vector<BlockRefer
   for (const BlockReference &block : blocks) {
     const StorageBlock &b = *block;
     const auto term_agrees = [&](const ComparisonPredicate &term, bool nulls_allowed, bool like) {
+      if (term.operand != nullptr) {
+        // a unary operation of the attribute: plain stripes in every block, or a dictionary the term can be evaluated over in
+        // every block (the other compressed forms take the per-block path and its decoded stripe); no order is used
+        CheckUnaryTerm(term, b.getRelation());
+        if (!nulls_allowed && b.nullBitmap(term.attribute) != nullptr) return false;
+        if (b.numTuples() == 0) return true;
+        const CompressedAttribute *cb = b.compressedAttribute(term.attribute);
+        if (cb != nullptr && !UnaryOnDictionary(b, term.attribute, b.getRelation().getAttributeType(term.attribute))) return false;
+        if (reference_block == nullptr) reference_block = &b;
+        const CompressedAttribute *cf = reference_block->compressedAttribute(term.attribute);
+        return (cb != nullptr) == (cf != nullptr) && (cb == nullptr || cb->code_width == cf->code_width);
+      }
       const Type &t = b.getRelation().getAttributeType(term.attribute);
       if (like) CheckLikeTerm(term, t);
       if (term.rhs_attribute != kInvalidAttributeID) {
@@ -547,7 +695,7 @@ void SelectTermForRun(const std::vector<BlockReference> &blocks, const std::vect
                       const ComparisonPredicate &term, const InListLiterals *in, const std::uint64_t *const *in_filters,
                       std::uint64_t *const *outs, std::int64_t *counts, TermScratch *scratch) {
   const std::size_t nb = blocks.size();
-  if (in == nullptr && term.rhs_attribute != kInvalidAttributeID) {
+  if (in == nullptr && term.operand == nullptr && term.rhs_attribute != kInvalidAttributeID) {
     // attribute OP attribute: one launch over the run, every block's two operands as that block holds them
     std::vector<const StorageBlock *> plain(nb);
     for (std::size_t b = 0; b < nb; ++b) plain[b] = blocks[b].get();
@@ -556,13 +704,37 @@ void SelectTermForRun(const std::vector<BlockReference> &blocks, const std::vect
     return;
   }
   const Type &t = blocks.front()->getRelation().getAttributeType(term.attribute);
+  const bool unary = term.operand != nullptr;
+  Type operand_type = t;   // of a unary term: the operation's result
+  if (unary) {
+    operand_type = CheckUnaryTerm(term, blocks.front()->getRelation());
+    if (in == nullptr) CheckUnaryLiteral(operand_type, term.literal);
+    ++unary_run_evaluations;
+  }
+  const qsx_unary_operand_t unary_operand = unary ? UnaryOperandOf(*term.operand) : qsx_unary_operand_t{};
+  // a unary term over nb stripes (the run's column stripes, or its dictionaries) in one launch
+  const auto select_unary_blocks = [&](int width, const std::int64_t *stripe_rows, const void *const *cols, const std::uint64_t *const *filters,
+                                       std::uint64_t *const *bitmaps, std::int64_t *bitmap_counts) {
+    const bool text = operand_type.id == kChar;
+    if (in != nullptr) {
+      CheckStatus(qsx_select_in_unary_blocks(&unary_operand, width, static_cast<std::int64_t>(nb), stripe_rows, cols,
+                                             text ? static_cast<const void *>(in->slots.data()) : in->values.data(),
+                                             text ? in->lengths.data() : nullptr, in->count, 0, filters, bitmaps, bitmap_counts, CurrentStream()),
+                  "qsx_select_in_unary_blocks");
+    } else {
+      CheckStatus(qsx_select_cmp_unary_blocks(&unary_operand, width, static_cast<std::int64_t>(nb), stripe_rows, cols, static_cast<int>(term.comparison),
+                                              text ? static_cast<const void *>(term.literal.text.data()) : &term.literal.v.i32,
+                                              text ? static_cast<int>(term.literal.text.size()) : 0, filters, bitmaps, bitmap_counts, CurrentStream()),
+                  "qsx_select_cmp_unary_blocks");
+    }
+  };
   std::vector<const void *> stripes(nb);
   if (ref.compressedAttribute(term.attribute) == nullptr) {   // (a compressed sort column is searched on its codes)
     for (std::size_t b = 0; b < nb; ++b) stripes[b] = blocks[b]->stripe(term.attribute);
   }
-  const bool like = in == nullptr && IsLikeComparison(term.comparison);
+  const bool like = !unary && in == nullptr && IsLikeComparison(term.comparison);
   if (like) CheckLikeTerm(term, t);
-  const bool on_sort_column = term.attribute == ref.sortColumn();
+  const bool on_sort_column = !unary && term.attribute == ref.sortColumn();
   // the comparison rewritten on every block's own codes (CompressedTupleStorageSubBlock::getMatchesForPredicate)
   std::vector<std::int32_t> ops;
   std::vector<std::uint32_t> firsts, seconds;
@@ -590,9 +762,10 @@ void SelectTermForRun(const std::vector<BlockReference> &blocks, const std::vect
       }
     }
   };
-  if ((like || in != nullptr) && ref.compressedAttribute(term.attribute) != nullptr) {
-    // LIKE / IN on a dictionary-coded attribute (the sort column included): one launch matches the pattern or the list against
-    // the run's dictionaries — block b's code set —, one tests the code stripes for membership in their block's set
+  if ((like || in != nullptr || unary) && ref.compressedAttribute(term.attribute) != nullptr) {
+    // LIKE / IN / a unary term on a dictionary-coded attribute (the sort column included): one launch matches the pattern, the
+    // list or the term against the run's dictionaries — block b's code set —, one tests the code stripes for membership in
+    // their block's set
     std::vector<std::int64_t> dict_rows(nb, 0), num_codes(nb, 0);
     std::vector<const void *> dictionaries(nb, nullptr);
     std::vector<const std::uint32_t *> offsets(nb, nullptr);   // a VARCHAR attribute: the variable-length dictionaries of the run
@@ -623,7 +796,9 @@ void SelectTermForRun(const std::vector<BlockReference> &blocks, const std::vect
       sets[b] = static_cast<std::uint64_t *>(scratch->back()->ptr) + set_at;
       set_at += static_cast<std::size_t>((num_codes[b] + 63) / 64) + (num_codes[b] != 0 ? 1 : 0);
     }
-    if (variable) {
+    if (unary) {
+      select_unary_blocks(t.id == kDate ? 8 : value_width, dict_rows.data(), dictionaries.data(), nullptr, sets.data(), nullptr);
+    } else if (variable) {
       // every block's own variable-length dictionary, matched where the images hold them: one launch over the run
       CheckStatus(qsx_select_like_var_blocks(t.width, static_cast<std::int64_t>(nb), dict_rows.data(), offsets.data(), dictionaries.data(),
                                              value_bytes.data(), term.literal.text.data(), static_cast<int>(term.literal.text.size()),
@@ -644,6 +819,8 @@ void SelectTermForRun(const std::vector<BlockReference> &blocks, const std::vect
     CheckStatus(qsx_select_codes_in_set_blocks(ref.compressedAttribute(term.attribute)->code_width, static_cast<std::int64_t>(nb), rows.data(),
                                                stripes.data(), sets.data(), num_codes.data(), in_filters, outs, counts, CurrentStream()),
                 "qsx_select_codes_in_set_blocks");
+  } else if (unary) {
+    select_unary_blocks(UnaryStripeWidth(t), rows.data(), stripes.data(), in_filters, outs, counts);
   } else if (on_sort_column && ref.compressedAttribute(term.attribute) != nullptr) {
     // the sort column of compressed blocks: the comparison rewritten on every block's own codes, then one search per block on
     // the code stripes
@@ -1139,6 +1316,10 @@ CaseEvaluator::CaseEvaluator(const ScalarPtr &s, const CatalogRelation &relation
     for (const ComparisonPredicate &term : s->whens[k].first.conjuncts) when_terms.push_back(&term);
     if (s->whens[k].first.tree != nullptr) CollectLeafTerms(*s->whens[k].first.tree, &when_terms);
     for (const ComparisonPredicate *term : when_terms) {
+      if (term->operand != nullptr) {
+        CheckUnaryTerm(*term, relation);   // (the literals' types are checked where the WHEN is evaluated)
+        continue;
+      }
       if (IsLikeComparison(term->comparison)) CheckLikeTerm(*term, relation.getAttributeType(term->attribute));
       if (term->rhs_attribute != kInvalidAttributeID) CheckAttributeComparison(*term, relation);
     }

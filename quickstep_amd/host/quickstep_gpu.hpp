@@ -368,6 +368,8 @@ struct TypedLiteral {
 // a Predicate is a conjunction of those and, optionally, a tree of them under AND / OR / NOT (PredicateNode).  As the residual predicate of a join
 // (HashJoinOperator.cpp:510-524, Predicate::matchesForJoinedTuples) a term also says which side each
 // attribute comes from (Scalar::kLeftSide = probe, kRightSide = build) and may compare two attributes.
+class Scalar;
+typedef std::shared_ptr<const Scalar> ScalarPtr;   // (scalar expressions: further down)
 struct ComparisonPredicate {
   attribute_id attribute;
   ComparisonID comparison;
@@ -375,9 +377,19 @@ struct ComparisonPredicate {
   bool on_build_side = false;                          // join residuals only: `attribute` is of the build relation
   attribute_id rhs_attribute = kInvalidAttributeID;    // != invalid: attribute OP rhs_attribute (literal unused)
   bool rhs_on_build_side = false;
+  // Optional: the left operand as a scalar (the reference's ComparisonPredicate takes any Scalar there,
+  // ComparisonPredicate.cpp:209-240 over ScalarUnaryExpression::getAllValues).  null: `attribute`.  Otherwise exactly what
+  // UnaryResultType accepts — Scalar::DateExtract / Scalar::Substring of an attribute — against an INT resp. a CHAR literal:
+  // EXTRACT(YEAR FROM o_orderdate) = 1995, SUBSTRING(c_phone FROM 1 FOR 2) IN (..) (Q22).  `attribute` then names the
+  // operation's attribute (OnScalar sets it): its null bitmap is the term's.  Evaluated in one pass over the attribute's stripe
+  // (qsx_select_cmp_unary / qsx_select_in_unary), over the block's dictionary when the attribute is dictionary-coded, with no
+  // intermediate column.  Another scalar, LIKE / NOT LIKE, a literal of the wrong type, a VARCHAR attribute and a join's
+  // residual predicate are QSX_ERR_UNSUPPORTED; together with rhs_attribute it is QSX_ERR_INVALID_ARGUMENT.
+  ScalarPtr operand;
   ComparisonPredicate() = default;
   ComparisonPredicate(attribute_id a, ComparisonID c, TypedLiteral l, bool build_side = false)
       : attribute(a), comparison(c), literal(l), on_build_side(build_side) {}
+  static ComparisonPredicate OnScalar(ScalarPtr scalar, ComparisonID c, TypedLiteral l);
   static ComparisonPredicate Attributes(attribute_id lhs, bool lhs_on_build, ComparisonID c, attribute_id rhs, bool rhs_on_build) {
     ComparisonPredicate p(lhs, c, TypedLiteral::Long(0), lhs_on_build);
     p.rhs_attribute = rhs;
@@ -421,6 +433,12 @@ struct Predicate {
   static PredicateNodePtr Compare(attribute_id a, ComparisonID c, const TypedLiteral &l) { return Compare(ComparisonPredicate(a, c, l)); }
   static PredicateNodePtr In(attribute_id operand, std::vector<TypedLiteral> literals);
   static PredicateNodePtr NotIn(attribute_id operand, std::vector<TypedLiteral> literals) { return Not(In(operand, std::move(literals))); }
+  // the same over a unary operation of an attribute (ComparisonPredicate::operand)
+  static PredicateNodePtr Compare(ScalarPtr operand, ComparisonID c, const TypedLiteral &l) {
+    return Compare(ComparisonPredicate::OnScalar(std::move(operand), c, l));
+  }
+  static PredicateNodePtr In(ScalarPtr operand, std::vector<TypedLiteral> literals);
+  static PredicateNodePtr NotIn(ScalarPtr operand, std::vector<TypedLiteral> literals) { return Not(In(std::move(operand), std::move(literals))); }
   static PredicateNodePtr And(std::vector<PredicateNodePtr> children);
   static PredicateNodePtr Or(std::vector<PredicateNodePtr> children);
   static PredicateNodePtr Not(PredicateNodePtr child);
@@ -434,9 +452,13 @@ std::int64_t NumPredicateTreeRunEvaluations();
 // of blocks in one launch.
 std::int64_t NumAttributeComparisonBlockEvaluations();
 std::int64_t NumAttributeComparisonRunEvaluations();
+// The same for a term over a unary operation (ComparisonPredicate::operand): evaluated for one block, and over a run of blocks
+// in one launch (two where the blocks hold the attribute behind dictionaries: the code sets, then the code stripes).
+std::int64_t NumUnaryPredicateBlockEvaluations();
+std::int64_t NumUnaryPredicateRunEvaluations();
 // The terms of `predicate` a qsx_agg_config_t can hold (numeric attribute OP literal, at most QSX_MAX_PRED_TERMS) into
-// config->pred / num_pred_terms, columns named by column_of; everything else — CHAR(n) terms, attribute-vs-attribute, overflow,
-// a tree — into *external, to be evaluated by Predicate and handed to the update as its filter.  external == nullptr: the caller
+// config->pred / num_pred_terms, columns named by column_of; everything else — CHAR(n) terms, attribute-vs-attribute, terms over
+// a unary operation, overflow, a tree — into *external, to be evaluated by Predicate and handed to the update as its filter.  external == nullptr: the caller
 // has no such path, and a term or tree the struct cannot hold is QSX_ERR_UNSUPPORTED.
 void LowerPredicateToAggConfig(const Predicate &predicate, const CatalogRelation &relation, const std::function<int(attribute_id)> &column_of,
                                qsx_agg_config_t *config, Predicate *external);
@@ -499,8 +521,6 @@ typedef InsertDestination PartitionAwareInsertDestination;   // (one class: the 
 enum class BinaryOperationID { kAdd = 0, kSubtract, kMultiply, kDivide };
 // the unary operations of types/operations/unary_operations/ that have a device form (qsx_eval_date_extract, qsx_eval_substring)
 enum class UnaryOperationID { kDateExtract = 0, kSubstring };
-class Scalar;
-typedef std::shared_ptr<const Scalar> ScalarPtr;
 class Scalar {
  public:
   enum Kind { kAttribute, kLiteral, kBinaryExpression, kCaseExpression, kUnaryExpression };
@@ -529,8 +549,8 @@ class Scalar {
   // ATTRIBUTE, a DATE or a CHAR(n); the result is nullable exactly when the attribute is.  A unary scalar is the root of a
   // Select scalar or a group-by key (AggregationStateSpec::group_by_scalars); an EXTRACT may also be a leaf of an arithmetic
   // tree in a Select scalar (Select.test:688).  Anything else — another operand, a unary in a CASE, as an aggregate's
-  // argument, SUBSTRING inside arithmetic — is QSX_ERR_UNSUPPORTED.  Predicates compare attributes and literals only, so no
-  // unary reaches them.
+  // argument, SUBSTRING inside arithmetic — is QSX_ERR_UNSUPPORTED.  A unary of an attribute may also be the left operand
+  // of a predicate's term (ComparisonPredicate::operand), in a Select, an aggregation's predicate or the WHEN of a CASE.
   UnaryOperationID unary_operation = UnaryOperationID::kDateExtract;
   int date_extract_unit = QSX_DATE_YEAR;   // QSX_DATE_YEAR / QSX_DATE_MONTH (any other unit: QSX_ERR_UNSUPPORTED)
   int substring_start = 0, substring_length = 0;

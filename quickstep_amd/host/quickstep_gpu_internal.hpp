@@ -305,6 +305,11 @@ void CheckLikeTerm(const ComparisonPredicate &term, const Type &type);
 // attributes are `relation`'s own (no build side: QSX_ERR_INVALID_ARGUMENT), numeric with numeric or DATE with DATE, no LIKE
 // (QSX_ERR_UNSUPPORTED).
 void CheckAttributeComparison(const ComparisonPredicate &term, const CatalogRelation &relation);
+// A term over a unary operation (ComparisonPredicate::operand).  CheckUnaryTerm: the operand is EXTRACT / SUBSTRING of an attribute
+// that is no VARCHAR, the comparison no LIKE, no rhs_attribute; returns the operand's type (INT, CHAR(m)).  CheckUnaryLiteral: a
+// literal of that type.
+Type CheckUnaryTerm(const ComparisonPredicate &term, const CatalogRelation &relation);
+void CheckUnaryLiteral(const Type &operand_type, const TypedLiteral &literal);
 void SelectCharTerm(const ComparisonPredicate &term, const void *stripe, int width, std::int64_t n, const std::uint64_t *filter,
                     std::uint64_t *out_bitmap, std::int64_t *out_count);
 bool RunPredicateCovers(const Predicate &predicate, const std::vector<BlockReference> &blocks);

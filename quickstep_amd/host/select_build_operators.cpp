@@ -393,6 +393,7 @@ void SelectWorkOrder::executeOnHost() {
   if (predicate_ != nullptr) {
     if (predicate_->tree != nullptr) throw ExecutionError("a predicate tree (OR / NOT / IN) in the host plumbing mode", QSX_ERR_UNSUPPORTED);
     for (const ComparisonPredicate &term : predicate_->conjuncts) {
+      if (term.operand != nullptr) throw ExecutionError("a term over a unary operation in the host plumbing mode", QSX_ERR_UNSUPPORTED);
       const Type &t = block->getRelation().getAttributeType(term.attribute);
       if (IsLikeComparison(term.comparison)) throw ExecutionError("LIKE / NOT LIKE in the host plumbing mode", QSX_ERR_UNSUPPORTED);
       if (term.rhs_attribute != kInvalidAttributeID) throw ExecutionError("a comparison of two attributes in the host plumbing mode", QSX_ERR_UNSUPPORTED);

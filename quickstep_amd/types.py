@@ -20,6 +20,7 @@ MAX_IN_LIST = 32                                                    # QSX_MAX_IN
 MAX_BOOL_LEAVES, MAX_BOOL_INSTRS, MAX_BOOL_DEPTH = 32, 64, 8        # QSX_MAX_BOOL_* (qsx_bitmap_eval)
 BOOL_AND, BOOL_OR, BOOL_NOT = -1, -2, -3                            # QSX_BOOL_* postfix codes of qsx_bitmap_eval
 DATE_YEAR, DATE_MONTH = 0, 1                                        # QSX_DATE_YEAR / QSX_DATE_MONTH (qsx_eval_date_extract)
+UNARY_DATE_FIELD, UNARY_SUBSTRING = 0, 1                            # QSX_UNARY_* (qsx_select_cmp_unary, qsx_select_in_unary)
 # qsx_agg_strategy_t
 AGG_SINGLE_STATE, AGG_COMPACT_KEY, AGG_COLLISION_FREE, AGG_GENERIC = range(4)
 # qsx_agg_fn_t
@@ -53,6 +54,21 @@ GROUPS_HASH_COLLISION = -1   # qsx_agg_finalize's group count when a wide-key st
 
 class Operand(C.Structure):
     _fields_ = [("kind", C.c_int32), ("index", C.c_int32)]
+
+
+class UnaryOperand(C.Structure):
+    """qsx_unary_operand_t: the left operand of qsx_select_cmp_unary / qsx_select_in_unary."""
+    _fields_ = [("kind", C.c_int32), ("unit", C.c_int32), ("start", C.c_int32), ("length", C.c_int32)]
+
+
+def date_field(unit):
+    """EXTRACT(unit FROM date) as a predicate's operand: unit is DATE_YEAR or DATE_MONTH."""
+    return UnaryOperand(UNARY_DATE_FIELD, int(unit), 0, 0)
+
+
+def substring_of(start, length):
+    """SUBSTRING(char FROM start + 1 FOR length) as a predicate's operand: start is 0-based."""
+    return UnaryOperand(UNARY_SUBSTRING, 0, int(start), int(length))
 
 
 class ExprInstr(C.Structure):

@@ -376,153 +376,248 @@ void CollectLeafTerms(const PredicateNode &node, std::vector<const ComparisonPre
 
 typedef std::vector<std::unique_ptr<DeviceBuffer>> TermScratch;   // what queued kernels of a term still read
 
-// An IN list over a stripe of values (a column stripe, or a dictionary: then the result is that dictionary's code set).
-void SelectInList(const InListLiterals &in, const Type &t, const void *stripe, int char_width, std::int64_t n, const std::uint64_t *filter,
-                  std::uint64_t *out_bitmap, std::int64_t *out_count) {
-  if (t.id == kChar) {
-    CheckStatus(qsx_select_in_char(stripe, char_width, n, in.slots.data(), in.lengths.data(), in.count, 0, filter, out_bitmap, out_count, CurrentStream()),
-                "qsx_select_in_char");
-  } else {
-    CheckStatus(qsx_select_in(t.id, stripe, n, in.values.data(), in.count, 0, filter, out_bitmap, out_count, CurrentStream()), "qsx_select_in");
-  }
-}
+// The blocks a term is evaluated over.  `run` false: ONE block (nb == 1), the single-stripe entry points; `run` true: a run of
+// blocks, the _blocks entry points — also when the run happens to hold one block.  `ref`: the block a term is classified
+// against — the block itself, or the first non-empty block of a run (RunPredicateCovers made the others agree with it).
+struct BlockSpan {
+  const StorageBlock *const *blocks;
+  std::size_t nb;
+  const std::int64_t *rows;
+  const StorageBlock *ref;
+  bool run;
+};
 
-// A term over a unary operation against a stripe of the operation's attribute (a column stripe, or a dictionary: then the result
-// is that dictionary's code set).  in != nullptr: the IN list.
-void SelectUnaryTerm(const ComparisonPredicate &term, const Type &operand_type, const InListLiterals *in, const void *stripe, int width,
-                     std::int64_t n, const std::uint64_t *filter, std::uint64_t *out_bitmap, std::int64_t *out_count) {
-  const qsx_unary_operand_t operand = UnaryOperandOf(*term.operand);
-  const bool text = operand_type.id == kChar;
-  if (in != nullptr) {
-    CheckStatus(qsx_select_in_unary(&operand, stripe, width, n, text ? static_cast<const void *>(in->slots.data()) : in->values.data(),
-                                    text ? in->lengths.data() : nullptr, in->count, 0, filter, out_bitmap, out_count, CurrentStream()),
-                "qsx_select_in_unary");
-  } else {
-    CheckStatus(qsx_select_cmp_unary(&operand, stripe, width, n, static_cast<int>(term.comparison),
-                                     text ? static_cast<const void *>(term.literal.text.data()) : &term.literal.v.i32,
-                                     text ? static_cast<int>(term.literal.text.size()) : 0, filter, out_bitmap, out_count, CurrentStream()),
-                "qsx_select_cmp_unary");
-  }
-}
-
-// ONE term over ONE block into a bitmap — the place both the conjunction chain and the leaves of a tree go through: plain
-// stripes, CHAR(n), LIKE, compressed attributes with the comparison rewritten on the block's codes, the search on the sort
-// column, and the code set of a LIKE or an IN list against the block's dictionary.  in != nullptr: `term.attribute IN (..)`.
-// NULLs are the caller's.
-void SelectTermForBlock(const StorageBlock &block, const ComparisonPredicate &term, const InListLiterals *in, const std::uint64_t *filter,
-                        std::uint64_t *out_bitmap, std::int64_t *out_count, TermScratch *scratch) {
-  const std::int64_t n = block.numTuples();
+// ONE term over a span of blocks into block b's bitmap outs[b] behind filters[b] (filters, or an entry of it, may be null) —
+// the one place that turns a term into bitmaps: the conjunction chains and the leaves of a tree, per block and over a run, go
+// through it.  One launch (two for a code set); in != nullptr: `term.attribute IN (..)`.  NULLs are the caller's.  The term is
+// classified once, against span.ref; the two callers differ only where an entry point is called: a block takes qsx_select_*
+// with cols[0], rows[0], its filter and outs[0], a run takes qsx_select_*_blocks.
+void SelectTerm(const BlockSpan &span, const ComparisonPredicate &term, const InListLiterals *in, const std::uint64_t *const *filters,
+                std::uint64_t *const *outs, std::int64_t *counts, TermScratch *scratch) {
+  const std::size_t nb = span.nb;
+  const std::int64_t num_blocks = static_cast<std::int64_t>(nb);
+  const bool run = span.run;
+  const StorageBlock &ref = *span.ref;
+  const qsx_stream_t stream = CurrentStream();
   if (in == nullptr && term.operand == nullptr && term.rhs_attribute != kInvalidAttributeID) {
-    // attribute OP attribute (ComparisonPredicate.cpp:243-333): both sides as the block holds them, the run form with one block
-    const StorageBlock *one = &block;
-    SelectAttributeComparison(&one, 1, &n, term, filter != nullptr ? &filter : nullptr, &out_bitmap, out_count);
-    ++attribute_comparison_block_evaluations;
+    // attribute OP attribute (ComparisonPredicate.cpp:243-333): one launch, every block's two operands as that block holds them
+    SelectAttributeComparison(span.blocks, nb, span.rows, term, filters, outs, counts);
+    ++(run ? attribute_comparison_run_evaluations : attribute_comparison_block_evaluations);
     return;
   }
-  if (term.operand != nullptr) {
-    // a unary operation of the attribute on the left (ComparisonPredicate.cpp:209-240 over ScalarUnaryExpression::getAllValues):
-    // one pass over the stripe, or over the block's dictionary (the term's code set) and then the code stripe; any other
-    // compressed form is read as the decoded stripe
-    const Type operand_type = CheckUnaryTerm(term, block.getRelation());
-    if (in == nullptr) CheckUnaryLiteral(operand_type, term.literal);
-    const Type &attribute_type = block.getRelation().getAttributeType(term.attribute);
-    if (UnaryOnDictionary(block, term.attribute, attribute_type)) {
-      const CompressedAttribute *dict = block.compressedAttribute(term.attribute);
-      scratch->emplace_back(new DeviceBuffer(static_cast<std::size_t>((dict->num_codes + 63) / 64) * 8 + 8));
-      std::uint64_t *set = static_cast<std::uint64_t *>(scratch->back()->ptr);
-      SelectUnaryTerm(term, operand_type, in, dict->dictionary, attribute_type.id == kDate ? 8 : dict->value_width, dict->num_codes, nullptr, set, nullptr);
-      CheckStatus(qsx_select_codes_in_set(dict->code_width, dict->codes, n, set, dict->num_codes, filter, out_bitmap, out_count, CurrentStream()),
-                  "qsx_select_codes_in_set");
-    } else {
-      SelectUnaryTerm(term, operand_type, in, block.stripe(term.attribute), UnaryStripeWidth(attribute_type), n, filter, out_bitmap, out_count);
-    }
-    ++unary_block_evaluations;
-    return;
-  }
-  const Type &t = block.getRelation().getAttributeType(term.attribute);
-  const bool like = in == nullptr && IsLikeComparison(term.comparison);
+  const bool unary = term.operand != nullptr;
+  // (a unary term is checked before anything asks for its attribute: an operand CheckUnaryTerm refuses names none)
+  const Type unary_type = unary ? CheckUnaryTerm(term, ref.getRelation()) : Type::Int();
+  if (unary && in == nullptr) CheckUnaryLiteral(unary_type, term.literal);
+  const Type &t = ref.getRelation().getAttributeType(term.attribute);
+  const Type &operand_type = unary ? unary_type : t;   // of a unary term: the operation's result
+  const bool like = !unary && in == nullptr && IsLikeComparison(term.comparison);
   if (like) CheckLikeTerm(term, t);
-  const CompressedAttribute *c = block.compressedAttribute(term.attribute);
-  if (c != nullptr && (like || (in != nullptr && c->kind == CompressedAttribute::kDictionary))) {
-    // LIKE / IN on a dictionary-coded attribute: the pattern or the list against the block's dictionary once (its matches are
-    // a set of codes), then code membership over the code stripe — on the sort column too, a set is no range.  The reference
-    // runs the matcher on every decompressed value (PatternMatchingComparators-inl.hpp:190-268); the values are not
-    // materialized here.
-    scratch->emplace_back(new DeviceBuffer(static_cast<std::size_t>((c->num_codes + 63) / 64) * 8 + 8));
-    std::uint64_t *set = static_cast<std::uint64_t *>(scratch->back()->ptr);
-    if (c->variable_length) {
-      // a VARCHAR attribute: the pattern against the entries of the variable-length dictionary where the image holds them
-      if (!like) throw ExecutionError("IN list on a VARCHAR attribute", QSX_ERR_UNSUPPORTED);
-      CheckStatus(qsx_select_like_var(c->variable_offsets, c->variable_values, c->num_codes, static_cast<std::int64_t>(c->variable_value_bytes),
-                                      t.width, term.literal.text.data(), static_cast<int>(term.literal.text.size()),
-                                      term.comparison == ComparisonID::kNotLike ? 1 : 0, nullptr, set, nullptr, CurrentStream()),
-                  "qsx_select_like_var");
+  const int comparison = static_cast<int>(term.comparison), negate = term.comparison == ComparisonID::kNotLike ? 1 : 0;
+  const int literal_length = static_cast<int>(term.literal.text.size());
+  const std::uint64_t *const filter0 = filters != nullptr ? filters[0] : nullptr;   // (of a block)
+
+  // The term against nb stripes of values — the column stripes, or the dictionaries: then the bitmaps are the blocks' code
+  // sets.  A unary operation of the attribute (ComparisonPredicate.cpp:209-240 over ScalarUnaryExpression::getAllValues), an
+  // IN list, LIKE (PatternMatchingUncheckedComparator, PatternMatchingComparators-inl.hpp:190-268) or CHAR(n) OP string
+  // literal (AsciiStringUncheckedComparator, AsciiStringComparators.hpp:218-251).
+  const auto select_values = [&](int width, const std::int64_t *n, const void *const *cols, const std::uint64_t *const *f,
+                                 std::uint64_t *const *bitmaps, std::int64_t *bitmap_counts) {
+    const std::uint64_t *const f0 = f != nullptr ? f[0] : nullptr;
+    if (unary) {
+      const qsx_unary_operand_t operand = UnaryOperandOf(*term.operand);
+      const bool text = operand_type.id == kChar;
+      if (in != nullptr) {
+        const void *literals = text ? static_cast<const void *>(in->slots.data()) : in->values.data();
+        const std::int32_t *lengths = text ? in->lengths.data() : nullptr;
+        CheckStatus(run ? qsx_select_in_unary_blocks(&operand, width, num_blocks, n, cols, literals, lengths, in->count, 0, f, bitmaps, bitmap_counts, stream)
+                        : qsx_select_in_unary(&operand, cols[0], width, n[0], literals, lengths, in->count, 0, f0, bitmaps[0], bitmap_counts, stream),
+                    run ? "qsx_select_in_unary_blocks" : "qsx_select_in_unary");
+      } else {
+        const void *literal = text ? static_cast<const void *>(term.literal.text.data()) : &term.literal.v.i32;
+        const int length = text ? literal_length : 0;
+        CheckStatus(run ? qsx_select_cmp_unary_blocks(&operand, width, num_blocks, n, cols, comparison, literal, length, f, bitmaps, bitmap_counts, stream)
+                        : qsx_select_cmp_unary(&operand, cols[0], width, n[0], comparison, literal, length, f0, bitmaps[0], bitmap_counts, stream),
+                    run ? "qsx_select_cmp_unary_blocks" : "qsx_select_cmp_unary");
+      }
+    } else if (in != nullptr && t.id == kChar) {
+      CheckStatus(run ? qsx_select_in_char_blocks(width, num_blocks, n, cols, in->slots.data(), in->lengths.data(), in->count, 0, f, bitmaps, bitmap_counts, stream)
+                      : qsx_select_in_char(cols[0], width, n[0], in->slots.data(), in->lengths.data(), in->count, 0, f0, bitmaps[0], bitmap_counts, stream),
+                  run ? "qsx_select_in_char_blocks" : "qsx_select_in_char");
+    } else if (in != nullptr) {
+      CheckStatus(run ? qsx_select_in_blocks(t.id, num_blocks, n, cols, in->values.data(), in->count, 0, f, bitmaps, bitmap_counts, stream)
+                      : qsx_select_in(t.id, cols[0], n[0], in->values.data(), in->count, 0, f0, bitmaps[0], bitmap_counts, stream),
+                  run ? "qsx_select_in_blocks" : "qsx_select_in");
+    } else if (!run) {
+      SelectCharTerm(term, cols[0], width, n[0], f0, bitmaps[0], bitmap_counts);   // (qsx_select_like / qsx_select_cmp_char)
     } else if (like) {
-      SelectCharTerm(term, c->dictionary, c->value_width, c->num_codes, nullptr, set, nullptr);
+      CheckStatus(qsx_select_like_blocks(width, num_blocks, n, cols, term.literal.text.data(), literal_length, negate, f, bitmaps, bitmap_counts, stream),
+                  "qsx_select_like_blocks");
     } else {
-      SelectInList(*in, t, c->dictionary, c->value_width, c->num_codes, nullptr, set, nullptr);
+      CheckStatus(qsx_select_cmp_char_blocks(width, num_blocks, n, cols, comparison, term.literal.text.data(), literal_length, f, bitmaps, bitmap_counts,
+                                             stream), "qsx_select_cmp_char_blocks");
     }
-    CheckStatus(qsx_select_codes_in_set(c->code_width, c->codes, n, set, c->num_codes, filter, out_bitmap, out_count, CurrentStream()),
-                "qsx_select_codes_in_set");
-  } else if (c != nullptr) {
+  };
+
+  const CompressedAttribute *c = ref.compressedAttribute(term.attribute);   // (an empty single block has none: the plain entries with n = 0)
+  // A term whose matches are a set of the dictionary's codes: LIKE, an IN list on a dictionary, a unary term on a dictionary it can
+  // be evaluated over (UnaryOnDictionary: fixed-width, and 8-byte aligned if of dates) — on the sort column too, a set is no range.
+  const bool code_set = unary ? UnaryOnDictionary(ref, term.attribute, t)
+                              : c != nullptr && (like || (in != nullptr && c->kind == CompressedAttribute::kDictionary));
+  if (code_set) {
+    // The pattern, the list or the term against every block's dictionary once — block b's code set —, then the code stripes
+    // tested for membership in their block's set.  The reference runs the matcher on every decompressed value
+    // (PatternMatchingComparators-inl.hpp:190-268); the values are not materialized here.
+    const bool variable = c->variable_length;   // a VARCHAR attribute: the variable-length dictionaries where the images hold them
+    if (variable && !like) throw ExecutionError("IN list on a VARCHAR attribute", QSX_ERR_UNSUPPORTED);
+    std::vector<std::int64_t> num_codes(nb, 0), value_bytes(nb, 0);
+    std::vector<const void *> codes(nb, nullptr), dictionaries(nb, nullptr);
+    std::vector<const std::uint32_t *> offsets(nb, nullptr);
+    std::vector<std::uint64_t *> sets(nb, nullptr);
+    std::size_t set_words = 0;
+    int value_width = t.width;
+    for (std::size_t b = 0; b < nb; ++b) {
+      const CompressedAttribute *cb = span.blocks[b]->compressedAttribute(term.attribute);
+      if (cb == nullptr) continue;   // (an empty block of a run)
+      codes[b] = cb->codes;
+      num_codes[b] = cb->num_codes;
+      if (!variable) {
+        dictionaries[b] = cb->dictionary;
+        value_width = cb->value_width;
+      } else if (cb->num_codes != 0) {
+        dictionaries[b] = cb->variable_values;
+        offsets[b] = cb->variable_offsets;
+        value_bytes[b] = static_cast<std::int64_t>(cb->variable_value_bytes);
+      }
+      set_words += static_cast<std::size_t>((cb->num_codes + 63) / 64) + 1;
+    }
+    // (num_codes + 63) / 64 words and one more per set; a run's buffer ends in one more word
+    scratch->emplace_back(new DeviceBuffer(set_words * 8 + (run ? 8 : 0)));
+    std::size_t set_at = 0;
+    for (std::size_t b = 0; b < nb; ++b) {
+      sets[b] = static_cast<std::uint64_t *>(scratch->back()->ptr) + set_at;
+      set_at += static_cast<std::size_t>((num_codes[b] + 63) / 64) + (num_codes[b] != 0 ? 1 : 0);
+    }
+    if (variable) {   // (a block passes its dictionary as it is, a run NULLs for a dictionary without entries)
+      CheckStatus(run ? qsx_select_like_var_blocks(t.width, num_blocks, num_codes.data(), offsets.data(), dictionaries.data(), value_bytes.data(),
+                                                   term.literal.text.data(), literal_length, negate, nullptr, sets.data(), nullptr, stream)
+                      : qsx_select_like_var(c->variable_offsets, c->variable_values, c->num_codes, static_cast<std::int64_t>(c->variable_value_bytes),
+                                            t.width, term.literal.text.data(), literal_length, negate, nullptr, sets[0], nullptr, stream),
+                  run ? "qsx_select_like_var_blocks" : "qsx_select_like_var");
+    } else {
+      select_values(unary && t.id == kDate ? 8 : value_width, num_codes.data(), dictionaries.data(), nullptr, sets.data(), nullptr);
+    }
+    CheckStatus(run ? qsx_select_codes_in_set_blocks(c->code_width, num_blocks, span.rows, codes.data(), sets.data(), num_codes.data(), filters, outs,
+                                                     counts, stream)
+                    : qsx_select_codes_in_set(c->code_width, codes[0], span.rows[0], sets[0], num_codes[0], filter0, outs[0], counts, stream),
+                run ? "qsx_select_codes_in_set_blocks" : "qsx_select_codes_in_set");
+  } else if (c != nullptr && !unary) {
+    // CompressedTupleStorageSubBlock::getMatchesForPredicate (storage/CompressedTupleStorageSubBlock.cpp:160-250): the
+    // comparison rewritten on every block's own codes, then the code stripes scanned — or, on the sort column of a compressed
+    // store, searched: the codes ascend, the matches are one range (CompressedColumnStoreTupleStorageSubBlock.cpp:420-760).
+    // (An IN list over truncated codes is K equalities in the tree's program: TreeCompiler, expand_in.)
     if (in != nullptr) throw ExecutionError("IN list over a truncated attribute reached the leaf evaluator", QSX_ERR_INVALID_ARGUMENT);
-    // CompressedTupleStorageSubBlock::getMatchesForPredicate (storage/CompressedTupleStorageSubBlock.cpp:160-250):
-    // rewrite to a comparison on codes, scan the code stripe
-    const PredicateTransformResult r = TransformPredicateOnCompressedAttribute(*c, t.id, term.comparison, term.literal);
-    if (r.type == PredicateTransformResult::kAll || r.type == PredicateTransformResult::kNone) {
-      // every code / no code: code >= 0 resp. code < 0
-      CheckStatus(qsx_select_codes(c->code_width, c->codes, n, r.type == PredicateTransformResult::kAll ? QSX_CODE_GE : QSX_CODE_LT, 0, 0,
-                                   filter, out_bitmap, out_count, CurrentStream()), "qsx_select_codes");
-    } else if (term.attribute == block.sortColumn()) {
-      // the sort column of a compressed store: the codes ascend, the matches are one range (the sort-column branches of
-      // CompressedColumnStoreTupleStorageSubBlock.cpp:420-760)
-      CheckStatus(qsx_select_codes_sorted(c->code_width, c->codes, n, r.comp, r.first_literal, r.second_literal, filter, out_bitmap, out_count,
-                                          CurrentStream()), "qsx_select_codes_sorted");
-    } else {
-      CheckStatus(qsx_select_codes(c->code_width, c->codes, n, r.comp, r.first_literal, r.second_literal, filter, out_bitmap, out_count,
-                                   CurrentStream()), "qsx_select_codes");
+    std::vector<const void *> codes(nb, nullptr);
+    std::vector<std::int32_t> ops(nb, QSX_CODE_LT);   // (an empty block of a run: no code)
+    std::vector<std::uint32_t> firsts(nb, 0), seconds(nb, 0);
+    bool all_or_none = false;   // (of the last block)
+    for (std::size_t b = 0; b < nb; ++b) {
+      const CompressedAttribute *cb = span.blocks[b]->compressedAttribute(term.attribute);
+      if (cb == nullptr) continue;
+      const PredicateTransformResult r = TransformPredicateOnCompressedAttribute(*cb, t.id, term.comparison, term.literal);
+      codes[b] = cb->codes;
+      all_or_none = r.type == PredicateTransformResult::kAll || r.type == PredicateTransformResult::kNone;
+      if (all_or_none) {
+        ops[b] = r.type == PredicateTransformResult::kAll ? QSX_CODE_GE : QSX_CODE_LT;   // every code / no code: code >= 0 resp. code < 0
+      } else {
+        ops[b] = r.comp;
+        firsts[b] = r.first_literal;
+        seconds[b] = r.second_literal;
+      }
     }
-  } else if (in != nullptr) {
-    SelectInList(*in, t, block.stripe(term.attribute), t.width, n, filter, out_bitmap, out_count);
-  } else if (IsTextType(t.id)) {   // (a plain VARCHAR(n) stripe holds CHAR(n) fields)
-    SelectCharTerm(term, block.stripe(term.attribute), t.width, n, filter, out_bitmap, out_count);
-  } else if (term.attribute == block.sortColumn()) {
-    // the block is sorted on this attribute: SortColumnPredicateEvaluator (storage/ColumnStoreUtil.cpp:40-280)
-    CheckStatus(qsx_select_cmp_sorted(t.id, block.stripe(term.attribute), n, static_cast<int>(term.comparison), &term.literal.v, filter, out_bitmap,
-                                      out_count, CurrentStream()), "qsx_select_cmp_sorted");
+    // A single block whose rewrite is every code / no code is scanned on its sort column too; a run searches every block.
+    if (term.attribute == ref.sortColumn() && (run || !all_or_none)) {
+      CheckStatus(run ? qsx_select_codes_sorted_blocks(c->code_width, num_blocks, span.rows, codes.data(), ops.data(), firsts.data(), seconds.data(),
+                                                       filters, outs, counts, stream)
+                      : qsx_select_codes_sorted(c->code_width, codes[0], span.rows[0], ops[0], firsts[0], seconds[0], filter0, outs[0], counts, stream),
+                  run ? "qsx_select_codes_sorted_blocks" : "qsx_select_codes_sorted");
+    } else {
+      CheckStatus(run ? qsx_select_codes_blocks(c->code_width, num_blocks, span.rows, codes.data(), ops.data(), firsts.data(), seconds.data(), filters,
+                                                outs, counts, stream)
+                      : qsx_select_codes(c->code_width, codes[0], span.rows[0], ops[0], firsts[0], seconds[0], filter0, outs[0], counts, stream),
+                  run ? "qsx_select_codes_blocks" : "qsx_select_codes");
+    }
   } else {
-    CheckStatus(qsx_select_cmp(t.id, block.stripe(term.attribute), n, static_cast<int>(term.comparison), &term.literal.v, filter, out_bitmap,
-                               out_count, CurrentStream()), "qsx_select_cmp");
+    // Stripes of values.  For a unary term on a compressed attribute without a dictionary it can be evaluated over (truncated
+    // values, a variable-length dictionary, a date dictionary that is not 8-byte aligned) stripe() is the decoded stripe: a
+    // single block reads it, RunPredicateCovers keeps that shape off the run path.
+    std::vector<const void *> stripes(nb);
+    for (std::size_t b = 0; b < nb; ++b) stripes[b] = span.blocks[b]->stripe(term.attribute);
+    if (unary || in != nullptr || IsTextType(t.id)) {   // (a plain VARCHAR(n) stripe holds CHAR(n) fields)
+      select_values(unary ? UnaryStripeWidth(t) : t.width, span.rows, stripes.data(), filters, outs, counts);
+    } else if (term.attribute == ref.sortColumn()) {
+      // the blocks are sorted on this attribute: SortColumnPredicateEvaluator (storage/ColumnStoreUtil.cpp:40-280), one search per block
+      CheckStatus(run ? qsx_select_cmp_sorted_blocks(t.id, num_blocks, span.rows, stripes.data(), comparison, &term.literal.v, filters, outs, counts, stream)
+                      : qsx_select_cmp_sorted(t.id, stripes[0], span.rows[0], comparison, &term.literal.v, filter0, outs[0], counts, stream),
+                  run ? "qsx_select_cmp_sorted_blocks" : "qsx_select_cmp_sorted");
+    } else {
+      CheckStatus(run ? qsx_select_cmp_blocks(t.id, num_blocks, span.rows, stripes.data(), comparison, &term.literal.v, filters, outs, counts, stream)
+                      : qsx_select_cmp(t.id, stripes[0], span.rows[0], comparison, &term.literal.v, filter0, outs[0], counts, stream),
+                  run ? "qsx_select_cmp_blocks" : "qsx_select_cmp");
+    }
   }
+  if (unary) ++(run ? unary_run_evaluations : unary_block_evaluations);
 }
 
-// The tree over one block: every leaf without a filter into a bitmap of its own, a nullable attribute's null bitmap as one more
-// leaf, one qsx_bitmap_eval behind `filter`.  What the queued kernels read goes to `scratch`.
-void EvaluateTreeForBlock(const PredicateNode &tree, const StorageBlock &block, const std::uint64_t *filter, std::uint64_t *out_bitmap,
-                          std::int64_t *out_count, TermScratch *scratch) {
-  const std::int64_t n = block.numTuples();
+// The tree over a span of blocks: every leaf without a filter into bitmaps of its own (SelectTerm), a nullable attribute's null
+// bitmap as one more leaf, then ONE qsx_bitmap_eval(_blocks) behind `filters` into outs / counts.  What the queued kernels read
+// goes to `scratch`.
+void EvaluateTree(const BlockSpan &span, const PredicateNode &tree, const std::uint64_t *const *filters, std::uint64_t *const *outs,
+                  std::int64_t *counts, TermScratch *scratch) {
+  const std::size_t nb = span.nb;
   TreeProgram compiled;
-  TreeCompiler(block.getRelation(), [&](attribute_id a) { return block.nullBitmap(a) != nullptr; },
+  TreeCompiler(span.ref->getRelation(),
                [&](attribute_id a) {
-                 const CompressedAttribute *c = block.compressedAttribute(a);
-                 return c != nullptr && c->kind != CompressedAttribute::kDictionary;
+                 for (std::size_t b = 0; b < nb; ++b) if (span.blocks[b]->nullBitmap(a) != nullptr) return true;
+                 return false;
+               },
+               [&](attribute_id a) {   // one program for the span: equalities as soon as one block's codes are truncated values
+                 for (std::size_t b = 0; b < nb; ++b) {
+                   // (a run passes over its empty blocks; a single block is asked whatever it holds)
+                   const CompressedAttribute *c = span.run && span.blocks[b]->numTuples() == 0 ? nullptr : span.blocks[b]->compressedAttribute(a);
+                   if (c != nullptr && c->kind != CompressedAttribute::kDictionary) return true;
+                 }
+                 return false;
                }, &compiled).compile(tree);
-  const std::size_t words = static_cast<std::size_t>((n + 63) / 64) + 1;
-  scratch->emplace_back(new DeviceBuffer(compiled.leaves.size() * words * 8 + 8));
-  std::uint64_t *next_leaf = static_cast<std::uint64_t *>(scratch->back()->ptr);
-  std::vector<const std::uint64_t *> leaves;
-  for (const TreeLeaf &leaf : compiled.leaves) {
-    if (leaf.null_of != kInvalidAttributeID) {
-      leaves.push_back(block.nullBitmap(leaf.null_of));
-      continue;
+  std::size_t bitmap_words = 0;
+  for (std::size_t b = 0; b < nb; ++b) bitmap_words += static_cast<std::size_t>((span.rows[b] + 63) / 64) + 1;
+  const std::size_t num_leaves = compiled.leaves.size();
+  scratch->emplace_back(new DeviceBuffer(num_leaves * bitmap_words * 8 + 8));
+  std::uint64_t *leaf_storage = static_cast<std::uint64_t *>(scratch->back()->ptr);
+  std::vector<const std::uint64_t *> block_leaves(nb * num_leaves, nullptr);   // block b's leaf k at [b * num_leaves + k]
+  std::vector<std::uint64_t *> leaf_outs(nb);
+  for (std::size_t k = 0; k < num_leaves; ++k) {
+    const TreeLeaf &leaf = compiled.leaves[k];
+    std::size_t leaf_at = k * bitmap_words;
+    for (std::size_t b = 0; b < nb; ++b) {
+      leaf_outs[b] = leaf_storage + leaf_at;
+      leaf_at += static_cast<std::size_t>((span.rows[b] + 63) / 64) + 1;
+      // NULL is the all-zero leaf: for a block without a null bitmap, and for every leaf of a run's empty block
+      if (span.run && span.rows[b] == 0) continue;
+      block_leaves[b * num_leaves + k] = leaf.null_of != kInvalidAttributeID ? span.blocks[b]->nullBitmap(leaf.null_of) : leaf_outs[b];
     }
-    SelectTermForBlock(block, leaf.term, leaf.in.get(), nullptr, next_leaf, nullptr, scratch);
-    leaves.push_back(next_leaf);
-    next_leaf += words;
+    if (leaf.null_of == kInvalidAttributeID) SelectTerm(span, leaf.term, leaf.in.get(), nullptr, leaf_outs.data(), nullptr, scratch);
   }
-  CheckStatus(qsx_bitmap_eval(static_cast<int>(leaves.size()), leaves.data(), static_cast<int>(compiled.program.size()), compiled.program.data(), n,
-                              filter, out_bitmap, out_count, CurrentStream()), "qsx_bitmap_eval");
-  ++tree_block_evaluations;
+  if (span.run) {
+    CheckStatus(qsx_bitmap_eval_blocks(static_cast<int>(num_leaves), static_cast<int>(compiled.program.size()), compiled.program.data(),
+                                       static_cast<std::int64_t>(nb), span.rows, block_leaves.data(), filters, outs, counts, CurrentStream()),
+                "qsx_bitmap_eval_blocks");
+    ++tree_run_evaluations;
+  } else {
+    CheckStatus(qsx_bitmap_eval(static_cast<int>(num_leaves), block_leaves.data(), static_cast<int>(compiled.program.size()), compiled.program.data(),
+                                span.rows[0], filters != nullptr ? filters[0] : nullptr, outs[0], counts, CurrentStream()), "qsx_bitmap_eval");
+    ++tree_block_evaluations;
+  }
 }
 }  // namespace
 
@@ -578,11 +673,14 @@ void *Predicate::getMatchesForBlock(const StorageBlock &block, std::int64_t *num
   bool first = true;
   bool recount = false;
   TermScratch scratch;   // code sets, leaf bitmaps (read by queued kernels: kept until the count has been read)
+  const StorageBlock *const one = &block;
+  const BlockSpan span{&one, 1, &n, one, false};   // (a block, not a run of one: the single-stripe entry points)
   try {
     for (const ComparisonPredicate &term : conjuncts) {
       const std::uint64_t *in = first ? filter : static_cast<const std::uint64_t *>(current);
+      std::uint64_t *const out = static_cast<std::uint64_t *>(next);
       // conjunctions chain the filter through their children (short-circuit)
-      SelectTermForBlock(block, term, nullptr, in, static_cast<std::uint64_t *>(next), static_cast<std::int64_t *>(count), &scratch);
+      SelectTerm(span, term, nullptr, in != nullptr ? &in : nullptr, &out, static_cast<std::int64_t *>(count), &scratch);
       // a comparison with NULL is not true (LiteralComparators-inl.hpp:330-370: the nullable variants test the value
       // pointer first): the stripe holds an arbitrary value under a NULL, so its match is taken back — for either operand of a
       // comparison of two attributes
@@ -598,8 +696,9 @@ void *Predicate::getMatchesForBlock(const StorageBlock &block, std::int64_t *num
     if (tree != nullptr) {
       // AND(conjuncts) AND tree: the chain's result (or the incoming filter) is the evaluator's filter, applied once at the root —
       // leaves are pure functions of the row, so this equals the reference's short-circuit filtering
-      EvaluateTreeForBlock(*tree, block, first ? filter : static_cast<const std::uint64_t *>(current), static_cast<std::uint64_t *>(next),
-                           static_cast<std::int64_t *>(count), &scratch);
+      const std::uint64_t *in = first ? filter : static_cast<const std::uint64_t *>(current);
+      std::uint64_t *const out = static_cast<std::uint64_t *>(next);
+      EvaluateTree(span, *tree, in != nullptr ? &in : nullptr, &out, static_cast<std::int64_t *>(count), &scratch);
       std::swap(current, next);
       first = false;
       recount = false;   // (the evaluator counted)
@@ -687,180 +786,6 @@ bool RunPredicateCovers(const Predicate &predicate, const std::vector<BlockRefer
   return true;
 }
 
-namespace {
-// ONE term over a RUN of blocks, one launch (two for a code set): block b's bitmap into outs[b] behind in_filters[b].  The run
-// counterpart of SelectTermForBlock, used by the conjunction chain and by the leaves of a tree.  `ref`: the first non-empty
-// block (RunPredicateCovers made the others agree with it).
-void SelectTermForRun(const std::vector<BlockReference> &blocks, const std::vector<std::int64_t> &rows, const StorageBlock &ref,
-                      const ComparisonPredicate &term, const InListLiterals *in, const std::uint64_t *const *in_filters,
-                      std::uint64_t *const *outs, std::int64_t *counts, TermScratch *scratch) {
-  const std::size_t nb = blocks.size();
-  if (in == nullptr && term.operand == nullptr && term.rhs_attribute != kInvalidAttributeID) {
-    // attribute OP attribute: one launch over the run, every block's two operands as that block holds them
-    std::vector<const StorageBlock *> plain(nb);
-    for (std::size_t b = 0; b < nb; ++b) plain[b] = blocks[b].get();
-    SelectAttributeComparison(plain.data(), nb, rows.data(), term, in_filters, outs, counts);
-    ++attribute_comparison_run_evaluations;
-    return;
-  }
-  const Type &t = blocks.front()->getRelation().getAttributeType(term.attribute);
-  const bool unary = term.operand != nullptr;
-  Type operand_type = t;   // of a unary term: the operation's result
-  if (unary) {
-    operand_type = CheckUnaryTerm(term, blocks.front()->getRelation());
-    if (in == nullptr) CheckUnaryLiteral(operand_type, term.literal);
-    ++unary_run_evaluations;
-  }
-  const qsx_unary_operand_t unary_operand = unary ? UnaryOperandOf(*term.operand) : qsx_unary_operand_t{};
-  // a unary term over nb stripes (the run's column stripes, or its dictionaries) in one launch
-  const auto select_unary_blocks = [&](int width, const std::int64_t *stripe_rows, const void *const *cols, const std::uint64_t *const *filters,
-                                       std::uint64_t *const *bitmaps, std::int64_t *bitmap_counts) {
-    const bool text = operand_type.id == kChar;
-    if (in != nullptr) {
-      CheckStatus(qsx_select_in_unary_blocks(&unary_operand, width, static_cast<std::int64_t>(nb), stripe_rows, cols,
-                                             text ? static_cast<const void *>(in->slots.data()) : in->values.data(),
-                                             text ? in->lengths.data() : nullptr, in->count, 0, filters, bitmaps, bitmap_counts, CurrentStream()),
-                  "qsx_select_in_unary_blocks");
-    } else {
-      CheckStatus(qsx_select_cmp_unary_blocks(&unary_operand, width, static_cast<std::int64_t>(nb), stripe_rows, cols, static_cast<int>(term.comparison),
-                                              text ? static_cast<const void *>(term.literal.text.data()) : &term.literal.v.i32,
-                                              text ? static_cast<int>(term.literal.text.size()) : 0, filters, bitmaps, bitmap_counts, CurrentStream()),
-                  "qsx_select_cmp_unary_blocks");
-    }
-  };
-  std::vector<const void *> stripes(nb);
-  if (ref.compressedAttribute(term.attribute) == nullptr) {   // (a compressed sort column is searched on its codes)
-    for (std::size_t b = 0; b < nb; ++b) stripes[b] = blocks[b]->stripe(term.attribute);
-  }
-  const bool like = !unary && in == nullptr && IsLikeComparison(term.comparison);
-  if (like) CheckLikeTerm(term, t);
-  const bool on_sort_column = !unary && term.attribute == ref.sortColumn();
-  // the comparison rewritten on every block's own codes (CompressedTupleStorageSubBlock::getMatchesForPredicate)
-  std::vector<std::int32_t> ops;
-  std::vector<std::uint32_t> firsts, seconds;
-  const auto rewrite_per_block = [&]() {
-    ops.resize(nb);
-    firsts.resize(nb);
-    seconds.resize(nb);
-    for (std::size_t b = 0; b < nb; ++b) {
-      const CompressedAttribute *c = blocks[b]->compressedAttribute(term.attribute);
-      if (c == nullptr) {   // an empty block
-        stripes[b] = nullptr;
-        ops[b] = QSX_CODE_LT;
-        firsts[b] = seconds[b] = 0;
-        continue;
-      }
-      const PredicateTransformResult r = TransformPredicateOnCompressedAttribute(*c, t.id, term.comparison, term.literal);
-      stripes[b] = c->codes;
-      if (r.type == PredicateTransformResult::kAll || r.type == PredicateTransformResult::kNone) {
-        ops[b] = r.type == PredicateTransformResult::kAll ? QSX_CODE_GE : QSX_CODE_LT;   // every code / no code
-        firsts[b] = seconds[b] = 0;
-      } else {
-        ops[b] = r.comp;
-        firsts[b] = r.first_literal;
-        seconds[b] = r.second_literal;
-      }
-    }
-  };
-  if ((like || in != nullptr || unary) && ref.compressedAttribute(term.attribute) != nullptr) {
-    // LIKE / IN / a unary term on a dictionary-coded attribute (the sort column included): one launch matches the pattern, the
-    // list or the term against the run's dictionaries — block b's code set —, one tests the code stripes for membership in
-    // their block's set
-    std::vector<std::int64_t> dict_rows(nb, 0), num_codes(nb, 0);
-    std::vector<const void *> dictionaries(nb, nullptr);
-    std::vector<const std::uint32_t *> offsets(nb, nullptr);   // a VARCHAR attribute: the variable-length dictionaries of the run
-    std::vector<std::int64_t> value_bytes(nb, 0);
-    std::vector<std::uint64_t *> sets(nb, nullptr);
-    std::size_t set_words = 0;
-    int value_width = t.width;
-    const bool variable = t.id == kVarChar;
-    if (variable && !like) throw ExecutionError("IN list on a VARCHAR attribute", QSX_ERR_UNSUPPORTED);
-    for (std::size_t b = 0; b < nb; ++b) {
-      const CompressedAttribute *c = blocks[b]->compressedAttribute(term.attribute);
-      stripes[b] = c != nullptr ? c->codes : nullptr;   // (nullptr: an empty block)
-      if (c == nullptr) continue;
-      dict_rows[b] = num_codes[b] = c->num_codes;
-      if (variable) {
-        dictionaries[b] = c->num_codes != 0 ? c->variable_values : nullptr;
-        offsets[b] = c->num_codes != 0 ? c->variable_offsets : nullptr;
-        value_bytes[b] = c->num_codes != 0 ? static_cast<std::int64_t>(c->variable_value_bytes) : 0;
-      } else {
-        dictionaries[b] = c->dictionary;
-        value_width = c->value_width;
-      }
-      set_words += static_cast<std::size_t>((c->num_codes + 63) / 64) + 1;
-    }
-    scratch->emplace_back(new DeviceBuffer(set_words * 8 + 8));
-    std::size_t set_at = 0;
-    for (std::size_t b = 0; b < nb; ++b) {
-      sets[b] = static_cast<std::uint64_t *>(scratch->back()->ptr) + set_at;
-      set_at += static_cast<std::size_t>((num_codes[b] + 63) / 64) + (num_codes[b] != 0 ? 1 : 0);
-    }
-    if (unary) {
-      select_unary_blocks(t.id == kDate ? 8 : value_width, dict_rows.data(), dictionaries.data(), nullptr, sets.data(), nullptr);
-    } else if (variable) {
-      // every block's own variable-length dictionary, matched where the images hold them: one launch over the run
-      CheckStatus(qsx_select_like_var_blocks(t.width, static_cast<std::int64_t>(nb), dict_rows.data(), offsets.data(), dictionaries.data(),
-                                             value_bytes.data(), term.literal.text.data(), static_cast<int>(term.literal.text.size()),
-                                             term.comparison == ComparisonID::kNotLike ? 1 : 0, nullptr, sets.data(), nullptr, CurrentStream()),
-                  "qsx_select_like_var_blocks");
-    } else if (like) {
-      CheckStatus(qsx_select_like_blocks(value_width, static_cast<std::int64_t>(nb), dict_rows.data(), dictionaries.data(), term.literal.text.data(),
-                                         static_cast<int>(term.literal.text.size()), term.comparison == ComparisonID::kNotLike ? 1 : 0, nullptr,
-                                         sets.data(), nullptr, CurrentStream()), "qsx_select_like_blocks");
-    } else if (t.id == kChar) {
-      CheckStatus(qsx_select_in_char_blocks(value_width, static_cast<std::int64_t>(nb), dict_rows.data(), dictionaries.data(), in->slots.data(),
-                                            in->lengths.data(), in->count, 0, nullptr, sets.data(), nullptr, CurrentStream()),
-                  "qsx_select_in_char_blocks");
-    } else {
-      CheckStatus(qsx_select_in_blocks(t.id, static_cast<std::int64_t>(nb), dict_rows.data(), dictionaries.data(), in->values.data(), in->count, 0,
-                                       nullptr, sets.data(), nullptr, CurrentStream()), "qsx_select_in_blocks");
-    }
-    CheckStatus(qsx_select_codes_in_set_blocks(ref.compressedAttribute(term.attribute)->code_width, static_cast<std::int64_t>(nb), rows.data(),
-                                               stripes.data(), sets.data(), num_codes.data(), in_filters, outs, counts, CurrentStream()),
-                "qsx_select_codes_in_set_blocks");
-  } else if (unary) {
-    select_unary_blocks(UnaryStripeWidth(t), rows.data(), stripes.data(), in_filters, outs, counts);
-  } else if (on_sort_column && ref.compressedAttribute(term.attribute) != nullptr) {
-    // the sort column of compressed blocks: the comparison rewritten on every block's own codes, then one search per block on
-    // the code stripes
-    rewrite_per_block();
-    CheckStatus(qsx_select_codes_sorted_blocks(ref.compressedAttribute(term.attribute)->code_width, static_cast<std::int64_t>(nb),
-                                               rows.data(), stripes.data(), ops.data(), firsts.data(), seconds.data(), in_filters, outs, counts,
-                                               CurrentStream()), "qsx_select_codes_sorted_blocks");
-  } else if (ref.compressedAttribute(term.attribute) != nullptr) {
-    // a compressed attribute: every block's code stripe scanned with the comparison rewritten on that block's codes
-    rewrite_per_block();
-    CheckStatus(qsx_select_codes_blocks(ref.compressedAttribute(term.attribute)->code_width, static_cast<std::int64_t>(nb), rows.data(),
-                                        stripes.data(), ops.data(), firsts.data(), seconds.data(), in_filters, outs, counts, CurrentStream()),
-                "qsx_select_codes_blocks");
-  } else if (in != nullptr && t.id == kChar) {
-    CheckStatus(qsx_select_in_char_blocks(t.width, static_cast<std::int64_t>(nb), rows.data(), stripes.data(), in->slots.data(), in->lengths.data(),
-                                          in->count, 0, in_filters, outs, counts, CurrentStream()), "qsx_select_in_char_blocks");
-  } else if (in != nullptr) {
-    CheckStatus(qsx_select_in_blocks(t.id, static_cast<std::int64_t>(nb), rows.data(), stripes.data(), in->values.data(), in->count, 0, in_filters,
-                                     outs, counts, CurrentStream()), "qsx_select_in_blocks");
-  } else if (like) {
-    // CHAR(n) LIKE pattern on plain stripes (PatternMatchingComparators-inl.hpp:190-268)
-    CheckStatus(qsx_select_like_blocks(t.width, static_cast<std::int64_t>(nb), rows.data(), stripes.data(), term.literal.text.data(),
-                                       static_cast<int>(term.literal.text.size()), term.comparison == ComparisonID::kNotLike ? 1 : 0, in_filters,
-                                       outs, counts, CurrentStream()), "qsx_select_like_blocks");
-  } else if (IsTextType(t.id)) {
-    // CHAR(n) OP string literal on plain stripes (AsciiStringUncheckedComparator, AsciiStringComparators.hpp:218-251)
-    CheckStatus(qsx_select_cmp_char_blocks(t.width, static_cast<std::int64_t>(nb), rows.data(), stripes.data(), static_cast<int>(term.comparison),
-                                           term.literal.text.data(), static_cast<int>(term.literal.text.size()), in_filters, outs, counts,
-                                           CurrentStream()), "qsx_select_cmp_char_blocks");
-  } else if (on_sort_column) {
-    // SortColumnPredicateEvaluator (storage/ColumnStoreUtil.cpp:40-280), one search per block
-    CheckStatus(qsx_select_cmp_sorted_blocks(t.id, static_cast<std::int64_t>(nb), rows.data(), stripes.data(), static_cast<int>(term.comparison),
-                                             &term.literal.v, in_filters, outs, counts, CurrentStream()), "qsx_select_cmp_sorted_blocks");
-  } else {
-    CheckStatus(qsx_select_cmp_blocks(t.id, static_cast<std::int64_t>(nb), rows.data(), stripes.data(), static_cast<int>(term.comparison),
-                                      &term.literal.v, in_filters, outs, counts, CurrentStream()), "qsx_select_cmp_blocks");
-  }
-}
-}  // namespace
-
 // The TupleIdSequences of the run's blocks under `predicate` (RunPredicateCovers said yes), every term one launch over the run,
 // chained like a conjunction behind `in_filters` (per block, entries may be null; or nullptr); then the tree: every leaf one
 // launch over the run into bitmaps of its own, and ONE qsx_bitmap_eval_blocks behind the chain's result.  out->bitmaps[b] is
@@ -870,10 +795,13 @@ void RunPredicateMatches(const Predicate &predicate, const std::vector<BlockRefe
   const std::size_t nb = blocks.size();
   std::size_t bitmap_words = 0;
   const StorageBlock *reference_block = blocks.empty() ? nullptr : blocks.front().get();
+  std::vector<const StorageBlock *> plain(nb);
   for (std::size_t b = 0; b < nb; ++b) {
+    plain[b] = blocks[b].get();
     bitmap_words += static_cast<std::size_t>((rows[b] + 63) / 64) + 1;
     if (reference_block != nullptr && reference_block->numTuples() == 0 && blocks[b]->numTuples() != 0) reference_block = blocks[b].get();
   }
+  const BlockSpan span{plain.data(), nb, rows.data(), reference_block, true};   // (a run, also when nb == 1: the _blocks entry points)
   // two sets of per-block bitmaps in two allocations, the terms ping-pong between them
   out->set_a.reset(new DeviceBuffer(bitmap_words * 8 + 8));
   out->set_b.reset(new DeviceBuffer(bitmap_words * 8 + 8));
@@ -888,49 +816,15 @@ void RunPredicateMatches(const Predicate &predicate, const std::vector<BlockRefe
   bool first = true;
   for (const ComparisonPredicate &term : predicate.conjuncts) {
     const std::uint64_t *const *in = first ? in_filters : reinterpret_cast<const std::uint64_t *const *>(cur.data());
-    SelectTermForRun(blocks, rows, *reference_block, term, nullptr, in, nxt.data(), static_cast<std::int64_t *>(out->counts->ptr), &out->scratch);
+    SelectTerm(span, term, nullptr, in, nxt.data(), static_cast<std::int64_t *>(out->counts->ptr), &out->scratch);
     std::swap(cur, nxt);
     first = false;
   }
   if (predicate.tree != nullptr && nb > 0) {
-    TreeProgram compiled;
-    TreeCompiler(blocks.front()->getRelation(),
-                 [&](attribute_id a) {
-                   for (const BlockReference &b : blocks) if (b->nullBitmap(a) != nullptr) return true;
-                   return false;
-                 },
-                 [&](attribute_id a) {   // one program for the run: equalities as soon as one block's codes are truncated values
-                   for (const BlockReference &b : blocks) {
-                     const CompressedAttribute *c = b->numTuples() > 0 ? b->compressedAttribute(a) : nullptr;
-                     if (c != nullptr && c->kind != CompressedAttribute::kDictionary) return true;
-                   }
-                   return false;
-                 }, &compiled).compile(*predicate.tree);
-    const std::size_t num_leaves = compiled.leaves.size();
-    out->scratch.emplace_back(new DeviceBuffer(num_leaves * bitmap_words * 8 + 8));
-    std::uint64_t *leaf_storage = static_cast<std::uint64_t *>(out->scratch.back()->ptr);
-    std::vector<const std::uint64_t *> block_leaves(nb * num_leaves, nullptr);
-    std::vector<std::uint64_t *> leaf_outs(nb);
-    for (std::size_t k = 0; k < num_leaves; ++k) {
-      const TreeLeaf &leaf = compiled.leaves[k];
-      if (leaf.null_of != kInvalidAttributeID) {   // (NULL for a block without a null bitmap: the all-zero leaf)
-        for (std::size_t b = 0; b < nb; ++b) block_leaves[b * num_leaves + k] = rows[b] > 0 ? blocks[b]->nullBitmap(leaf.null_of) : nullptr;
-        continue;
-      }
-      std::size_t leaf_at = k * bitmap_words;
-      for (std::size_t b = 0; b < nb; ++b) {
-        leaf_outs[b] = leaf_storage + leaf_at;
-        block_leaves[b * num_leaves + k] = rows[b] > 0 ? leaf_outs[b] : nullptr;
-        leaf_at += static_cast<std::size_t>((rows[b] + 63) / 64) + 1;
-      }
-      SelectTermForRun(blocks, rows, *reference_block, leaf.term, leaf.in.get(), nullptr, leaf_outs.data(), nullptr, &out->scratch);
-    }
-    const std::uint64_t *const *filters = first ? in_filters : reinterpret_cast<const std::uint64_t *const *>(cur.data());
-    CheckStatus(qsx_bitmap_eval_blocks(static_cast<int>(num_leaves), static_cast<int>(compiled.program.size()), compiled.program.data(),
-                                       static_cast<std::int64_t>(nb), rows.data(), block_leaves.data(), filters, nxt.data(),
-                                       static_cast<std::int64_t *>(out->counts->ptr), CurrentStream()), "qsx_bitmap_eval_blocks");
+    // AND(conjuncts) AND tree, as in getMatchesForBlock: the chain's result (or the incoming filters) is the evaluator's filter
+    EvaluateTree(span, *predicate.tree, first ? in_filters : reinterpret_cast<const std::uint64_t *const *>(cur.data()), nxt.data(),
+                 static_cast<std::int64_t *>(out->counts->ptr), &out->scratch);
     std::swap(cur, nxt);
-    ++tree_run_evaluations;
   }
   out->bitmaps = cur;
 }

@@ -290,7 +290,7 @@ void CheckRepartition(const char *op, bool has_repartition, const InsertDestinat
 struct RunMatches {
   std::unique_ptr<DeviceBuffer> set_a, set_b, counts;
   std::vector<std::uint64_t *> bitmaps;   // block b's bitmap under the whole conjunction
-  std::vector<std::unique_ptr<DeviceBuffer>> scratch;   // code sets of LIKE terms on coded attributes: read by queued kernels
+  std::vector<std::unique_ptr<DeviceBuffer>> scratch;   // code sets, a tree's leaf bitmaps: read by queued kernels
 };
 // LIKE / NOT LIKE terms (query_context.cpp).  CheckLikeTerm: QSX_ERR_UNSUPPORTED unless the term is CHAR(n) or VARCHAR(n)
 // attribute against a pattern literal of at most QSX_MAX_LIKE_PATTERN bytes.  SelectCharTerm: a CHAR(n) attribute against a string literal over a
@@ -312,6 +312,15 @@ Type CheckUnaryTerm(const ComparisonPredicate &term, const CatalogRelation &rela
 void CheckUnaryLiteral(const Type &operand_type, const TypedLiteral &literal);
 void SelectCharTerm(const ComparisonPredicate &term, const void *stripe, int width, std::int64_t n, const std::uint64_t *filter,
                     std::uint64_t *out_bitmap, std::int64_t *out_count);
+// ONE evaluator turns a term into bitmaps (query_context.cpp, SelectTerm over a BlockSpan) and ONE function evaluates a tree
+// (EvaluateTree); Predicate::getMatchesForBlock hands them a single block (the qsx_select_* entry points), RunPredicateMatches a
+// run (the _blocks entry points, also for a run of one block).  What differs between the two on purpose is marked where it
+// happens: a single block scans an every-code / no-code rewrite on a compressed sort column where a run searches; a unary term
+// on a compressed attribute without a dictionary it can be evaluated over (truncated values, a date dictionary that is not
+// 8-byte aligned) reads the decoded stripe() per block, and RunPredicateCovers keeps that shape off the run path; an IN list
+// over truncated codes that reaches the evaluator is QSX_ERR_INVALID_ARGUMENT, IN on VARCHAR QSX_ERR_UNSUPPORTED; an empty
+// single block has no compressed attribute and takes the plain entry with n = 0.
+// RunPredicateCovers: can the run forms evaluate `predicate` over these blocks in one launch per term?  RunPredicateMatches: do so.
 bool RunPredicateCovers(const Predicate &predicate, const std::vector<BlockReference> &blocks);
 void RunPredicateMatches(const Predicate &predicate, const std::vector<BlockReference> &blocks, const std::vector<std::int64_t> &rows,
                          const std::uint64_t *const *in_filters, RunMatches *out);

@@ -129,7 +129,7 @@ inline std::vector<unsigned char> HeaderCompressed(std::uint64_t num_slots, std:
   PutFixed64(&header, tuple_store_size);
   return header;
 }
-// columns / nulls as for Build(); the rows must be in ascending order of the sort attribute.  INT / LONG / DOUBLE attributes.
+// columns / nulls as for Build(); the rows must be in ascending order of the sort attribute.  INT / LONG / DOUBLE / DATE attributes.
 inline std::vector<unsigned char> BuildCompressed(const quickstep::CatalogRelation &relation, const std::vector<const void *> &columns,
                                                   const std::vector<std::vector<bool>> &nulls, std::int64_t num_tuples, std::size_t block_bytes,
                                                   int sort_attribute, const std::vector<Coding> &coding, std::int64_t *max_tuples_out = nullptr) {
@@ -149,6 +149,7 @@ inline std::vector<unsigned char> BuildCompressed(const quickstep::CatalogRelati
     switch (relation.getAttributeType(static_cast<quickstep::attribute_id>(a)).id) {
       case quickstep::kInt: return static_cast<std::int32_t>(x) < static_cast<std::int32_t>(y);
       case quickstep::kLong: return static_cast<std::int64_t>(x) < static_cast<std::int64_t>(y);
+      case quickstep::kDate: { quickstep::DateLit dx, dy; std::memcpy(&dx, &x, 8); std::memcpy(&dy, &y, 8); return dx < dy; }
       default: { double dx, dy; std::memcpy(&dx, &x, 8); std::memcpy(&dy, &y, 8); return dx < dy; }
     }
   };

@@ -4,13 +4,15 @@
 // one), EXTRACT(YEAR) = y, a range of two conjuncts, EXTRACT(MONTH) IN (..) — a few thousand rows in several small blocks, plain
 // and dictionary-compressed, per block and over a run (which must stay on the run path).  Then an aggregation whose predicate
 // holds such terms against exact integer sums, SUM(CASE WHEN EXTRACT(YEAR ..) = y THEN v ELSE 0 END), and every refusal with
-// its status and message.  Expected rows are computed here on the host columns.
+// its status and message.  And a DATE dictionary the term cannot be evaluated over — inside an adopted block image, at an address
+// that is no multiple of 8 —, where a block reads the decoded stripe.  Expected rows are computed here on the host columns.
 #include <algorithm>
 #include <cstring>
 #include <functional>
 #include <set>
 #include <string>
 
+#include "block_image_util.hpp"
 #include "test_util.hpp"
 
 using namespace quickstep;
@@ -258,6 +260,66 @@ void runAggregation(const Customers &t, bool compressed, std::size_t blocks_per_
   EXPECT_TRUE(got_1995 == static_cast<double>(want_1995));   // integers far below 2^53: exact in any order
 }
 
+// (id, o_orderdate) of the first four blocks as CompressedColumnStore images adopted in place, the dates behind 2-byte codes into
+// a dictionary that follows the image's protobuf header: it lies at an address that is no multiple of 8, and the date kernels
+// read 8-byte words.  UnaryOnDictionary says no, so a single block evaluates the term over the decoded stripe (stripe()), and
+// RunPredicateCovers sends a run block by block — the run counter must not move.  The empty block holds a dictionary without entries.
+void runAdoptedImages(const Customers &t, std::size_t blocks_per_order) {
+  struct Images {
+    std::vector<void *> dev;
+    ~Images() { for (void *p : dev) qsx_device_free(p); }
+  };
+  for (const bool as_tree : {false, true}) {
+    Images images;   // (outlives the storage manager whose blocks point into it)
+    CatalogRelation rel(1, "orders"), out(2, "out");
+    StorageManager storage;
+    rel.addAttribute("id", Type::Int());
+    rel.addAttribute("o_orderdate", Type::Date());
+    out.addAttribute("id", Type::Int());
+    block_image::Coding values, dictionary;
+    dictionary.kind = block_image::Coding::kDictionary;
+    dictionary.code_width = 2;
+    std::size_t loaded = 0;
+    for (const std::int64_t n : {2500, 1001, 0, 777}) {
+      const std::vector<unsigned char> image = block_image::BuildCompressed(rel, {t.id.data() + loaded, t.date.data() + loaded}, {{}, {}}, n,
+                                                                            std::size_t(1) << 21, 0, {values, dictionary});
+      void *dev = nullptr;
+      CheckStatus(qsx_device_alloc(image.size(), &dev), "qsx_device_alloc");
+      images.dev.push_back(dev);
+      CheckStatus(qsx_copy_to_device(dev, image.data(), image.size(), nullptr), "qsx_copy_to_device");
+      CheckStatus(qsx_stream_synchronize(nullptr), "qsx_stream_synchronize");
+      const BlockReference b = storage.getBlock(storage.adoptBlockImage(&rel, dev, image.size()));
+      const CompressedAttribute *c = b->compressedAttribute(1);
+      EXPECT_EQ(b->numTuples(), n);
+      EXPECT_TRUE(c != nullptr && c->kind == CompressedAttribute::kDictionary && (n == 0) == (c->num_codes == 0));
+      EXPECT_TRUE(c != nullptr && (reinterpret_cast<std::uintptr_t>(c->dictionary) & 7) != 0);
+      loaded += static_cast<std::size_t>(n);
+    }
+    const std::function<bool(std::size_t)> want = as_tree ? std::function<bool(std::size_t)>([&](std::size_t r) { return t.date[r].month == 1 || t.date[r].month == 6 || t.date[r].month == 12; })
+                                                          : std::function<bool(std::size_t)>([&](std::size_t r) { return t.date[r].year == 1995; });
+    QueryContext ctx;
+    const auto pred = ctx.addPredicate(as_tree ? P::Tree(P::In(Month(1), {I(1), I(6), I(12)}))
+                                               : Where({ComparisonPredicate::OnScalar(Year(1), ComparisonID::kEqual, I(1995))}));
+    const auto dest = ctx.addInsertDestination(&out, &storage);
+    SelectOperator select(0, rel, false, out, dest, pred, std::vector<attribute_id>{0}, true);
+    select.setBlocksPerWorkOrder(blocks_per_order);
+    const std::int64_t block_before = NumUnaryPredicateBlockEvaluations(), run_before = NumUnaryPredicateRunEvaluations();
+    fetchAndExecuteWorkOrders(&select, &ctx, &storage);
+    EXPECT_EQ(NumUnaryPredicateRunEvaluations() - run_before, std::int64_t(0));
+    EXPECT_EQ(NumUnaryPredicateBlockEvaluations() - block_before, std::int64_t(4));
+    std::size_t rows = 0, want_rows = 0;
+    const std::set<std::int32_t> ids = selectedIds(&storage, ctx.getInsertDestination(dest)->getTouchedBlocks(), &rows);
+    bool same = true;
+    for (std::size_t r = 0; r < loaded; ++r) {
+      want_rows += want(r);
+      if (want(r) != (ids.count(static_cast<std::int32_t>(r)) != 0)) same = false;
+    }
+    EXPECT_TRUE(same);
+    EXPECT_EQ(rows, want_rows);
+    EXPECT_TRUE(want_rows > 20 && want_rows < loaded);
+  }
+}
+
 int statusOf(const std::function<void()> &body, std::string *message) {
   message->clear();
   try {
@@ -391,6 +453,7 @@ int main() {
       runAggregation(t, compressed, per_order);
     }
   }
+  for (const std::size_t per_order : {std::size_t(1), std::size_t(5)}) runAdoptedImages(t, per_order);
   runRefusals(t);
   return finish("unary_predicate_operator_test");
 }

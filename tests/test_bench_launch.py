@@ -45,6 +45,8 @@ def test_loopback_transport_protocol_selftest():
     """tests/cpp/loopback: the stand-in for RCCL that lets several ranks share one GPU (QSX_RCCL_LIBRARY) — its rendezvous,
     grouped send / recv matching, collectives and reductions at world 1, 2, 3, with host memory in place of device memory."""
     exe = os.path.join(ROOT, "tests", "cpp", "bin", "loopback_selftest")
+    if not os.path.exists(exe):             # (like the host tests: a tree whose tests/cpp/bin was cleaned builds it again)
+        subprocess.run(["make", "-C", os.path.join(ROOT, "quickstep_amd", "host")], check=True)
     assert os.path.exists(exe), "make -C quickstep_amd/host builds it"
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "loopback selftest ok" in r.stdout, r.stdout + r.stderr

@@ -1238,7 +1238,9 @@ def test_date_predicate_and_date_group_keys(capi, oracle, dev, monkeypatch):
 
 def test_expression_projection_is_bit_equal_to_the_oracle(capi, oracle, dev):
     """qsx_eval_expression (ScalarBinaryExpression::getAllValues on its own): Q1's charge expression and a mixed-type one;
-    every node is rounded on its own in IEEE double on both sides, so the columns are bit-equal."""
+    every node is rounded on its own in IEEE double on both sides, so the columns are bit-equal.  The values here are benign:
+    tests/test_gpu_expression.py runs the programs that tell a contracted or reordered node, edge operands, every temp and the
+    integer entry point, against tests/expr_reference.py."""
     rng = np.random.default_rng(83)
     for n in (1, 63, 100_003):
         price = np.round(rng.uniform(900, 105000, size=n), 2)

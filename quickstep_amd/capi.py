@@ -227,6 +227,11 @@ if _lib.qsx_abi_sizeof_case_desc() != C.sizeof(T.CaseDesc):
 lib = _lib
 EXPORTED = tuple(_SIGNATURES)
 
+# the tests' hook into every form of K9 (csrc/partition.hip): not declared in include/qsx.h, so not in EXPORTED
+_lib.qsx_debug_partition_scatter.restype = _int
+_lib.qsx_debug_partition_scatter.argtypes = [_int, _int, _int, _pp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64), _i64, _int, _int,
+                                             _int, _i64, _int, _pp, C.POINTER(_i32), _pp, _vp, _vp]
+
 
 def _check(status, where):
     if status != T.OK:
@@ -1775,6 +1780,43 @@ def partition_scatter_blocks(block_keys, num_partitions, block_cols, stream=None
     _check(_lib.qsx_partition_scatter_blocks(qsx_type_of(block_keys[0]), nb, (C.c_int64 * nb)(*rows), _ptr_array(block_keys), num_partitions,
                                              ncols, _ptr_array(flat), widths, _ptr_array(out_cols), _ptr(offsets), _ptr(ws), ws_bytes,
                                              _stream(stream)), "qsx_partition_scatter_blocks")
+    return out_cols, offsets
+
+
+def debug_partition_scatter(form, key_cols, cols, num_partitions=64, key_shifts=None, shift=0, align_rows=0, max_chunks=0,
+                            out_cols=None, stream=None):
+    """qsx_debug_partition_scatter, the tests' hook into the forms of K9 that no entry point of their own reaches (csrc/partition.hip):
+    form 0 qsx_partition_scatter (key_cols = [INT or LONG stripe]); 1 the packed-key partitioning of the mid-size aggregation
+    (key_cols of 1 / 2 / 4 / 8-byte elements at key_shifts bits, align_rows); 2 one radix digit of key_cols = [64-bit keys] at
+    `shift`; 3 / 4 one digit of the packed keys' mixing hash, keeping the row order / not; 5 qsx_partition_scatter_blocks
+    (key_cols[b] block b's key stripe, cols[b][c] its column c).  max_chunks > 0 caps the number of chunks of the call (a
+    workgroup then walks several tiles).  out_cols: the output tensors (allocated here, n rows, when None).  Returns (out_cols,
+    int64[2 P + 1] on the device: P + 1 offsets, or with align_rows P piece starts and P counts; what the call did not write is -1)."""
+    nk = len(key_cols)
+    assert nk > 0 and all(k.is_contiguous() for k in key_cols)
+    device = key_cols[0].device
+    rows = None
+    if form == 5:
+        assert len(cols) == nk
+        rows = (C.c_int64 * nk)(*[k.numel() for k in key_cols])
+        n = sum(k.numel() for k in key_cols)
+        first = cols[0]
+        flat = [c for b in cols for c in b]
+    else:
+        n = key_cols[0].numel()
+        first = flat = list(cols)
+    assert all(c.is_contiguous() for c in flat)
+    ncols = len(first)
+    if out_cols is None:
+        out_cols = [torch.empty(n, dtype=c.dtype, device=device) for c in first]
+    widths = (C.c_int32 * max(ncols, 1))(*[c.element_size() for c in first])
+    kw = (C.c_int32 * nk)(*[k.element_size() for k in key_cols])
+    ks = (C.c_int32 * nk)(*(key_shifts if key_shifts is not None else [0] * nk))
+    offsets = torch.full((2 * num_partitions + 1,), -1, dtype=torch.int64, device=device)
+    key_type = qsx_type_of(key_cols[0]) if form in (0, 5) else T.LONG
+    _check(_lib.qsx_debug_partition_scatter(form, key_type, nk, _ptr_array(key_cols), kw, ks, rows, n, num_partitions, shift, align_rows,
+                                            max_chunks, ncols, _ptr_array(flat), widths, _ptr_array(out_cols), _ptr(offsets),
+                                            _stream(stream)), "qsx_debug_partition_scatter")
     return out_cols, offsets
 
 

@@ -695,7 +695,8 @@ __global__ __launch_bounds__(1024) void align_starts_kernel(int64_t *__restrict_
 
 static size_t p_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-static int64_t blocks_for(int64_t n) {
+// max_chunks > 0: at most that many chunks in this call (qsx_debug_partition_scatter: chunks of several tiles at test sizes).
+static int64_t blocks_for(int64_t n, int64_t max_chunks = 0) {
   // whole tiles per workgroup, at most 4096 workgroups
   int64_t G = (n + kPTile - 1) / kPTile;
   if (G < 1) G = 1;
@@ -704,6 +705,7 @@ static int64_t blocks_for(int64_t n) {
   // rows of (key, tid)); QSX_K9_GRID: sweeps
   static const int64_t cap = getenv("QSX_K9_GRID") != nullptr && atoll(getenv("QSX_K9_GRID")) > 0 ? atoll(getenv("QSX_K9_GRID")) : 2 * kMaxGridBlocks;
   if (G > cap) G = cap;
+  if (max_chunks > 0 && G > max_chunks) G = max_chunks;
   return G;
 }
 
@@ -714,8 +716,8 @@ size_t partition_workspace_bytes(int64_t n, int num_partitions) {
 }
 
 // The rows a workgroup takes: whole tiles, blocks_for(n) chunks over one stripe.
-static int64_t chunk_rows_for(int64_t n) {
-  const int64_t G = blocks_for(n);
+static int64_t chunk_rows_for(int64_t n, int64_t max_chunks = 0) {
+  const int64_t G = blocks_for(n, max_chunks);
   const int64_t rows_per_block = (n + G - 1) / G;
   return (rows_per_block + kPTile - 1) / kPTile * kPTile;
 }
@@ -732,11 +734,11 @@ size_t partition_blocks_workspace_bytes(int64_t n, int64_t num_blocks, int num_p
 template <typename Loader, int MODE>
 static int launch_partition_t(Loader keys, int64_t n, int P, int pow2, const ScatterArgs &args, int64_t *out_offsets,
                               void *workspace, int align_rows, hipStream_t s, const long long *runs_dev = nullptr,
-                              int64_t G_runs = 0, int64_t rows_runs = 0) {
+                              int64_t G_runs = 0, int64_t rows_runs = 0, int64_t max_chunks = 0) {
   constexpr bool kRunForms = MODE == 0 && !std::is_same<Loader, PackedKey>::value;   // (the C ABI's partition function only)
   if (runs_dev != nullptr && !kRunForms) return QSX_ERR_UNSUPPORTED;
-  const int64_t G = runs_dev != nullptr ? G_runs : blocks_for(n);
-  const int64_t rows_per_block = runs_dev != nullptr ? rows_runs : chunk_rows_for(n);
+  const int64_t G = runs_dev != nullptr ? G_runs : blocks_for(n, max_chunks);
+  const int64_t rows_per_block = runs_dev != nullptr ? rows_runs : chunk_rows_for(n, max_chunks);
   const int64_t cells = G * P;
   int64_t *starts = static_cast<int64_t *>(workspace);
   char *after = static_cast<char *>(workspace) + p_align_up(sizeof(int64_t) * (cells + 1), 256);
@@ -849,7 +851,7 @@ static int launch_partition_t(Loader keys, int64_t n, int P, int pow2, const Sca
 // the partitioned probe.
 int partition_scatter_impl(int mode, int key_type, const void *keys_dev, int64_t n, int num_partitions, int ncols,
                            const void *const *cols, const int32_t *widths, void *const *out_cols, int64_t *out_offsets_dev,
-                           void *workspace_dev, size_t workspace_bytes, hipStream_t s, int align_rows) {
+                           void *workspace_dev, size_t workspace_bytes, hipStream_t s, int align_rows, int64_t max_chunks) {
   if (n < 0 || num_partitions < 1 || ncols < 0 || ncols > QSX_MAX_COLUMNS || out_offsets_dev == nullptr) {
     return QSX_ERR_INVALID_ARGUMENT;
   }
@@ -884,18 +886,18 @@ int partition_scatter_impl(int mode, int key_type, const void *keys_dev, int64_t
   }
   if (key_type == QSX_INT) {
     const ColumnKey<int32_t> k{static_cast<const int32_t *>(keys_dev)};
-    return mode == 0 ? launch_partition_t<ColumnKey<int32_t>, 0>(k, n, num_partitions, pow2, args, out_offsets_dev, workspace_dev, align_rows, s)
-                     : launch_partition_t<ColumnKey<int32_t>, 1>(k, n, num_partitions, pow2, args, out_offsets_dev, workspace_dev, align_rows, s);
+    return mode == 0 ? launch_partition_t<ColumnKey<int32_t>, 0>(k, n, num_partitions, pow2, args, out_offsets_dev, workspace_dev, align_rows, s, nullptr, 0, 0, max_chunks)
+                     : launch_partition_t<ColumnKey<int32_t>, 1>(k, n, num_partitions, pow2, args, out_offsets_dev, workspace_dev, align_rows, s, nullptr, 0, 0, max_chunks);
   }
   const ColumnKey<int64_t> k{static_cast<const int64_t *>(keys_dev)};
-  return mode == 0 ? launch_partition_t<ColumnKey<int64_t>, 0>(k, n, num_partitions, pow2, args, out_offsets_dev, workspace_dev, align_rows, s)
-                   : launch_partition_t<ColumnKey<int64_t>, 1>(k, n, num_partitions, pow2, args, out_offsets_dev, workspace_dev, align_rows, s);
+  return mode == 0 ? launch_partition_t<ColumnKey<int64_t>, 0>(k, n, num_partitions, pow2, args, out_offsets_dev, workspace_dev, align_rows, s, nullptr, 0, 0, max_chunks)
+                   : launch_partition_t<ColumnKey<int64_t>, 1>(k, n, num_partitions, pow2, args, out_offsets_dev, workspace_dev, align_rows, s, nullptr, 0, 0, max_chunks);
 }
 
 // One stable LSD radix pass: rows ordered by the 6-bit digit (keys64 >> shift) & 63, ties in input order.
 int partition_scatter_digit(const unsigned long long *keys64_dev, int64_t n, int shift, int ncols, const void *const *cols,
                             const int32_t *widths, void *const *out_cols, int64_t *out_offsets_dev, void *workspace_dev,
-                            size_t workspace_bytes, hipStream_t s) {
+                            size_t workspace_bytes, hipStream_t s, int64_t max_chunks) {
   if (n <= 0 || ncols < 0 || ncols > QSX_MAX_COLUMNS || out_offsets_dev == nullptr || shift < 0 || shift > 63) return QSX_ERR_INVALID_ARGUMENT;
   if (workspace_bytes < partition_workspace_bytes(n, kWave) || workspace_dev == nullptr) return QSX_ERR_CAPACITY;
   ScatterArgs args;
@@ -906,14 +908,14 @@ int partition_scatter_digit(const unsigned long long *keys64_dev, int64_t n, int
     args.dst[c] = out_cols[c];
   }
   const ColumnKey<int64_t> k{reinterpret_cast<const int64_t *>(keys64_dev)};
-  return launch_partition_t<ColumnKey<int64_t>, 2>(k, n, kWave, shift, args, out_offsets_dev, workspace_dev, 0, s);
+  return launch_partition_t<ColumnKey<int64_t>, 2>(k, n, kWave, shift, args, out_offsets_dev, workspace_dev, 0, s, nullptr, 0, 0, max_chunks);
 }
 
 // Mixing-hash partitioning on a key code packed on the fly from up to QSX_MAX_KEYS key columns (mode 1 only).
 int partition_scatter_packed_keys(int num_keys, const void *const *key_cols, const int *key_widths, const int *key_shifts,
                                   int64_t n, int num_partitions, int ncols, const void *const *cols, const int32_t *widths,
                                   void *const *out_cols, int64_t *out_offsets_dev, void *workspace_dev, size_t workspace_bytes,
-                                  hipStream_t s, int align_rows) {
+                                  hipStream_t s, int align_rows, int64_t max_chunks) {
   if (n <= 0 || num_keys < 1 || num_keys > QSX_MAX_KEYS || num_partitions < 2 || num_partitions > kWave ||
       (num_partitions & (num_partitions - 1)) != 0 || ncols < 0 || ncols > QSX_MAX_COLUMNS || out_offsets_dev == nullptr) {
     return QSX_ERR_INVALID_ARGUMENT;
@@ -935,14 +937,15 @@ int partition_scatter_packed_keys(int num_keys, const void *const *key_cols, con
   }
   int log2p = 0;
   while ((1 << log2p) < num_partitions) ++log2p;
-  return launch_partition_t<PackedKey, 1>(k, n, num_partitions, log2p, args, out_offsets_dev, workspace_dev, align_rows, s);
+  return launch_partition_t<PackedKey, 1>(k, n, num_partitions, log2p, args, out_offsets_dev, workspace_dev, align_rows, s, nullptr, 0, 0, max_chunks);
 }
 
 // One pass of an LSD ordering by the mixing hash of a key code packed on the fly: 64 buckets by the digit (hash >> shift) & 63;
 // stable (every pass but the first has to be) or not.
 int partition_scatter_packed_digit(int num_keys, const void *const *key_cols, const int *key_widths, const int *key_shifts, int64_t n,
                                    int shift, bool stable, int ncols, const void *const *cols, const int32_t *widths, void *const *out_cols,
-                                   int64_t *out_offsets_dev, void *workspace_dev, size_t workspace_bytes, hipStream_t s) {
+                                   int64_t *out_offsets_dev, void *workspace_dev, size_t workspace_bytes, hipStream_t s,
+                                   int64_t max_chunks) {
   if (n <= 0 || num_keys < 1 || num_keys > QSX_MAX_KEYS || ncols < 0 || ncols > QSX_MAX_COLUMNS || out_offsets_dev == nullptr || shift < 0 || shift > 58) {
     return QSX_ERR_INVALID_ARGUMENT;
   }
@@ -961,37 +964,15 @@ int partition_scatter_packed_digit(int num_keys, const void *const *key_cols, co
     k.width[i] = i < num_keys ? key_widths[i] : 0;
     k.shift[i] = i < num_keys ? key_shifts[i] : 0;
   }
-  if (!stable) return launch_partition_t<PackedKey, 4>(k, n, kWave, shift, args, out_offsets_dev, workspace_dev, 0, s);
-  return launch_partition_t<PackedKey, 3>(k, n, kWave, shift, args, out_offsets_dev, workspace_dev, 0, s);
+  if (!stable) return launch_partition_t<PackedKey, 4>(k, n, kWave, shift, args, out_offsets_dev, workspace_dev, 0, s, nullptr, 0, 0, max_chunks);
+  return launch_partition_t<PackedKey, 3>(k, n, kWave, shift, args, out_offsets_dev, workspace_dev, 0, s, nullptr, 0, 0, max_chunks);
 }
 
-}  // namespace qsx
-
-using namespace qsx;
-
-extern "C" {
-
-size_t qsx_partition_workspace_bytes(int64_t n, int num_partitions) { return partition_workspace_bytes(n, num_partitions); }
-
-int qsx_partition_scatter(int key_type, const void *keys_dev, int64_t n, int num_partitions, int ncols,
-                          const void *const *cols, const int32_t *widths, void *const *out_cols,
-                          int64_t *out_offsets_dev, void *workspace_dev, size_t workspace_bytes,
-                          qsx_stream_t stream) {
-  QSX_REQUIRE_DEVICE();
-  return partition_scatter_impl(0, key_type, keys_dev, n, num_partitions, ncols, cols, widths, out_cols, out_offsets_dev,
-                                workspace_dev, workspace_bytes, as_stream(stream), 0);
-}
-
-size_t qsx_partition_blocks_workspace_bytes(int64_t n, int64_t num_blocks, int num_partitions) {
-  return partition_blocks_workspace_bytes(n, num_blocks < 0 ? 0 : num_blocks, num_partitions);
-}
-
-// K9 over a run of blocks: the result of qsx_partition_scatter over the blocks' rows laid end to end, without laying them so.
-int qsx_partition_scatter_blocks(int key_type, int64_t num_blocks, const int64_t *block_rows, const void *const *block_keys,
-                                 int num_partitions, int ncols, const void *const *block_cols, const int32_t *widths,
-                                 void *const *out_cols, int64_t *out_offsets_dev, void *workspace_dev, size_t workspace_bytes,
-                                 qsx_stream_t stream) {
-  QSX_REQUIRE_DEVICE();
+// K9 over a run of blocks (qsx_partition_scatter_blocks; the device is ready).
+static int partition_scatter_blocks_impl(int key_type, int64_t num_blocks, const int64_t *block_rows, const void *const *block_keys,
+                                         int num_partitions, int ncols, const void *const *block_cols, const int32_t *widths,
+                                         void *const *out_cols, int64_t *out_offsets_dev, void *workspace_dev, size_t workspace_bytes,
+                                         hipStream_t s, int64_t max_chunks) {
   if (num_blocks < 0 || num_partitions < 1 || ncols < 0 || ncols > QSX_MAX_COLUMNS || out_offsets_dev == nullptr ||
       (num_blocks > 0 && (block_rows == nullptr || block_keys == nullptr)) ||
       (ncols > 0 && (widths == nullptr || out_cols == nullptr || (num_blocks > 0 && block_cols == nullptr)))) {
@@ -999,7 +980,6 @@ int qsx_partition_scatter_blocks(int key_type, int64_t num_blocks, const int64_t
   }
   if (num_partitions > kWave) return QSX_ERR_UNSUPPORTED;
   if (key_type != QSX_INT && key_type != QSX_LONG) return QSX_ERR_UNSUPPORTED;
-  hipStream_t s = as_stream(stream);
   ScatterArgs args;
   args.ncols = ncols;
   for (int c = 0; c < ncols; ++c) {
@@ -1034,7 +1014,7 @@ int qsx_partition_scatter_blocks(int key_type, int64_t num_blocks, const int64_t
   for (int c = 0; c < ncols; ++c) {
     if (out_cols[c] == nullptr) return QSX_ERR_INVALID_ARGUMENT;
   }
-  const int64_t chunk_rows = chunk_rows_for(n);
+  const int64_t chunk_rows = chunk_rows_for(n, max_chunks);
   RunTable table;
   const long long chunks = table.build(chunk_rows, nb, rows.data(), keys.data(), nullptr, nullptr, nullptr);
   if (chunks <= 0) return QSX_ERR_INVALID_ARGUMENT;
@@ -1052,6 +1032,105 @@ int qsx_partition_scatter_blocks(int key_type, int64_t num_blocks, const int64_t
   }
   return launch_partition_t<ColumnKey<int64_t>, 0>(ColumnKey<int64_t>{nullptr}, n, num_partitions, is_pow2 ? 1 : 0, args, out_offsets_dev,
                                                    workspace_dev, 0, s, runs_dev, chunks, chunk_rows);
+}
+
+}  // namespace qsx
+
+using namespace qsx;
+
+extern "C" {
+
+size_t qsx_partition_workspace_bytes(int64_t n, int num_partitions) { return partition_workspace_bytes(n, num_partitions); }
+
+int qsx_partition_scatter(int key_type, const void *keys_dev, int64_t n, int num_partitions, int ncols,
+                          const void *const *cols, const int32_t *widths, void *const *out_cols,
+                          int64_t *out_offsets_dev, void *workspace_dev, size_t workspace_bytes,
+                          qsx_stream_t stream) {
+  QSX_REQUIRE_DEVICE();
+  return partition_scatter_impl(0, key_type, keys_dev, n, num_partitions, ncols, cols, widths, out_cols, out_offsets_dev,
+                                workspace_dev, workspace_bytes, as_stream(stream), 0);
+}
+
+size_t qsx_partition_blocks_workspace_bytes(int64_t n, int64_t num_blocks, int num_partitions) {
+  return partition_blocks_workspace_bytes(n, num_blocks < 0 ? 0 : num_blocks, num_partitions);
+}
+
+// K9 over a run of blocks: the result of qsx_partition_scatter over the blocks' rows laid end to end, without laying them so.
+int qsx_partition_scatter_blocks(int key_type, int64_t num_blocks, const int64_t *block_rows, const void *const *block_keys,
+                                 int num_partitions, int ncols, const void *const *block_cols, const int32_t *widths,
+                                 void *const *out_cols, int64_t *out_offsets_dev, void *workspace_dev, size_t workspace_bytes,
+                                 qsx_stream_t stream) {
+  QSX_REQUIRE_DEVICE();
+  return partition_scatter_blocks_impl(key_type, num_blocks, block_rows, block_keys, num_partitions, ncols, block_cols, widths, out_cols,
+                                       out_offsets_dev, workspace_dev, workspace_bytes, as_stream(stream), 0);
+}
+
+// The tests' way into every form of K9 (tests/test_gpu_partition_forms.py); like the other qsx_debug_* symbols not part of the
+// ABI (not in qsx.h).  On the caller's stream, with a workspace sized here.  form:
+//   0  qsx_partition_scatter: key_cols[0] = the stripe of key_type keys;
+//   1  partition_scatter_packed_keys: num_keys key columns of key_widths bytes at key_shifts bits, align_rows as there
+//      (> 0: out_offsets_dev receives 2 * num_partitions values, the output columns hold n + align_rows * num_partitions rows);
+//   2  partition_scatter_digit: key_cols[0] = 64-bit keys, the digit at `shift` (65 offsets);
+//   3  partition_scatter_packed_digit, stable;   4  the same, not stable (packed keys as in form 1, 65 offsets);
+//   5  qsx_partition_scatter_blocks: num_keys blocks, key_cols[b] block b's key stripe of block_rows[b] rows,
+//      cols[b * ncols + c] its column c (n is not read).
+// max_chunks: partition.hpp — 0 is what the library's own calls pass.
+int qsx_debug_partition_scatter(int form, int key_type, int num_keys, const void *const *key_cols, const int32_t *key_widths,
+                                const int32_t *key_shifts, const int64_t *block_rows, int64_t n, int num_partitions, int shift,
+                                int align_rows, int64_t max_chunks, int ncols, const void *const *cols, const int32_t *widths,
+                                void *const *out_cols, int64_t *out_offsets_dev, qsx_stream_t stream) {
+  QSX_REQUIRE_DEVICE();
+  if (form < 0 || form > 5 || max_chunks < 0 || align_rows < 0 || num_keys < 1 || key_cols == nullptr || ncols < 0 ||
+      ncols > QSX_MAX_COLUMNS || (ncols > 0 && (cols == nullptr || widths == nullptr || out_cols == nullptr))) {
+    return QSX_ERR_INVALID_ARGUMENT;
+  }
+  for (int c = 0; c < ncols; ++c) {
+    if (widths[c] != 1 && widths[c] != 2 && widths[c] != 4 && widths[c] != 8) return QSX_ERR_UNSUPPORTED;
+  }
+  const bool packed = form == 1 || form == 3 || form == 4;
+  int kw[QSX_MAX_KEYS] = {}, ks[QSX_MAX_KEYS] = {};
+  if (packed) {
+    if (num_keys > QSX_MAX_KEYS || key_widths == nullptr || key_shifts == nullptr) return QSX_ERR_INVALID_ARGUMENT;
+    for (int k = 0; k < num_keys; ++k) {
+      if (key_widths[k] != 1 && key_widths[k] != 2 && key_widths[k] != 4 && key_widths[k] != 8) return QSX_ERR_UNSUPPORTED;
+      if (key_shifts[k] < 0 || key_shifts[k] + 8 * key_widths[k] > 64) return QSX_ERR_INVALID_ARGUMENT;
+      kw[k] = key_widths[k];
+      ks[k] = key_shifts[k];
+    }
+  }
+  hipStream_t s = as_stream(stream);
+  size_t ws_bytes;
+  if (form == 5) {
+    if (block_rows == nullptr) return QSX_ERR_INVALID_ARGUMENT;
+    n = 0;
+    for (int b = 0; b < num_keys; ++b) n += block_rows[b] > 0 ? block_rows[b] : 0;
+    ws_bytes = partition_blocks_workspace_bytes(n, num_keys, num_partitions < 1 ? 1 : num_partitions);
+  } else {
+    if (n < 0) return QSX_ERR_INVALID_ARGUMENT;
+    ws_bytes = partition_workspace_bytes(n, form == 0 || form == 1 ? (num_partitions < 1 ? 1 : num_partitions) : kWave);
+  }
+  CallScratch scratch(s);
+  const int rc = scratch.reserve(ws_bytes);
+  if (rc != QSX_OK) return rc;
+  void *ws = scratch.take(ws_bytes);
+  switch (form) {
+    case 0:
+      return partition_scatter_impl(0, key_type, key_cols[0], n, num_partitions, ncols, cols, widths, out_cols, out_offsets_dev, ws,
+                                    ws_bytes, s, 0, max_chunks);
+    case 1:
+      return partition_scatter_packed_keys(num_keys, key_cols, kw, ks, n, num_partitions, ncols, cols, widths, out_cols,
+                                           out_offsets_dev, ws, ws_bytes, s, align_rows, max_chunks);
+    case 2:
+      return partition_scatter_digit(static_cast<const unsigned long long *>(key_cols[0]), n, shift, ncols, cols, widths, out_cols,
+                                     out_offsets_dev, ws, ws_bytes, s, max_chunks);
+    case 3:
+    case 4:
+      return partition_scatter_packed_digit(num_keys, key_cols, kw, ks, n, shift, form == 3, ncols, cols, widths, out_cols,
+                                            out_offsets_dev, ws, ws_bytes, s, max_chunks);
+    default:
+      return partition_scatter_blocks_impl(key_type, num_keys, block_rows, key_cols, num_partitions, ncols, cols, widths, out_cols,
+                                           out_offsets_dev, ws, ws_bytes, s, max_chunks);
+  }
 }
 
 }  // extern "C"

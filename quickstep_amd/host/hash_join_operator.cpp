@@ -97,9 +97,10 @@ namespace {
 // The build relation as gather segments (one per build block; the reference loops over build
 // blocks instead, HashJoinOperator.cpp:494-540).
 struct BuildSegments {
+  const CatalogRelation &relation;
   std::vector<BlockReference> refs;
   std::vector<std::int64_t> first_rows;
-  BuildSegments(const CatalogRelation &build_relation, StorageManager *storage_manager) {
+  BuildSegments(const CatalogRelation &build_relation, StorageManager *storage_manager) : relation(build_relation) {
     for (block_id b : build_relation.getBlocksSnapshot()) refs.push_back(storage_manager->getBlock(b));
     std::sort(refs.begin(), refs.end(),
               [](const BlockReference &a, const BlockReference &b) { return a->firstRow() < b->firstRow(); });
@@ -122,7 +123,71 @@ struct BuildSegments {
   }
 };
 
-// Joined pairs of one probe block, on device.
+// The probe tuples of one work order: a run of blocks whose tuple ids are run-global row numbers (block b's start at
+// first_rows[b]), or a single block outside a run (base 0).  Each form keeps its own entry points: a block is gathered from
+// its stripe, a run — also a run of one block — by one segmented gather over all blocks.
+struct ProbeSide {
+  const CatalogRelation &relation;
+  const bool run;
+  std::vector<BlockReference> blocks;
+  std::vector<std::int64_t> rows, first_rows;
+  std::int64_t total_rows = 0;
+  ProbeSide(const CatalogRelation &probe_relation, bool is_run) : relation(probe_relation), run(is_run) {}
+  // word_aligned: the join ends in ONE bitmap over the run's tuple ids — every block starts at a word boundary, so that its
+  // part of the bitmap is the bitmap of the block
+  void add(BlockReference block, bool word_aligned) {
+    rows.push_back(block->numTuples());
+    first_rows.push_back(total_rows);
+    total_rows += block->numTuples();
+    if (word_aligned) total_rows = (total_rows + 63) / 64 * 64;
+    blocks.push_back(std::move(block));
+  }
+  void gather(attribute_id attr, int width, const void *tids, std::int64_t n, void *dst) const {
+    if (!run) {
+      CheckStatus(qsx_gather(width, blocks.front()->stripe(attr), static_cast<const std::int32_t *>(tids), n, dst, CurrentStream()), "qsx_gather");
+      return;
+    }
+    std::vector<const void *> segs;
+    for (const BlockReference &b : blocks) segs.push_back(b->stripe(attr));
+    CheckStatus(qsx_gather_segmented(width, static_cast<int>(segs.size()), segs.data(), first_rows.data(),
+                                     static_cast<const std::int32_t *>(tids), n, dst, CurrentStream()),
+                "qsx_gather_segmented");
+  }
+  // null bits of a nullable probe attribute for n output tuples, by the tuple ids that gather its values, into out_words from
+  // bit out_first_bit on (an output block's bitmaps start zeroed: nothing to do when no block of a run has a bitmap)
+  void gatherNulls(attribute_id attr, const void *tids, std::int64_t n, std::uint64_t *out_words, std::int64_t out_first_bit = 0) const {
+    if (!relation.getAttributeType(attr).nullable || n == 0) return;
+    if (out_words == nullptr) throw ExecutionError("join output of a nullable attribute must be nullable", QSX_ERR_INVALID_ARGUMENT);
+    if (!run) {
+      GatherBlockNulls(*blocks.front(), attr, tids, n, out_words);
+      return;
+    }
+    // empty blocks share their first row with the next one: the gather wants strictly increasing segment starts
+    bool any = false;
+    std::vector<const std::uint64_t *> used_segs;
+    std::vector<std::int64_t> used_first;
+    for (std::size_t b = 0; b < blocks.size(); ++b) {
+      any = any || blocks[b]->nullBitmap(attr) != nullptr;
+      if (rows[b] == 0) continue;
+      used_segs.push_back(blocks[b]->nullBitmap(attr));
+      used_first.push_back(first_rows[b]);
+    }
+    if (!any) return;
+    if ((out_first_bit & 63) != 0) throw ExecutionError("join output null bits: unaligned tail", QSX_ERR_UNSUPPORTED);
+    CheckStatus(qsx_bitmap_gather_segmented(static_cast<int>(used_segs.size()), used_segs.data(), used_first.data(), static_cast<const std::int32_t *>(tids), n,
+                                            out_words + out_first_bit / 64, CurrentStream()), "qsx_bitmap_gather_segmented");
+  }
+};
+
+// Where the joined tuples go: output attribute i is attribute selection[i] of the build or of the probe side.
+struct JoinOutput {
+  const std::vector<attribute_id> &selection;
+  const std::vector<bool> &on_build;
+  InsertDestination *destination;
+  partition_id partition;
+};
+
+// Joined pairs of one work order, on device.
 struct JoinedPairs {
   std::unique_ptr<DeviceBuffer> probe_tids, build_tids;
   std::int64_t count = 0;
@@ -143,6 +208,147 @@ void CompactPairs(JoinedPairs *pairs, const void *bitmap) {
   pairs->count = ReadCount(count.ptr);
   pairs->probe_tids = std::move(p);
   pairs->build_tids = std::move(b);
+}
+
+// The terms evaluated on the pair list: the component equalities of a hashed composite key (`components`:
+// compositeKeyCollisionCheck, SeparateChainingHashTable.hpp:1046 — equal folds, equal components?), then the residual
+// conjuncts (matchesForJoinedTuples, :510-524).
+std::vector<ComparisonPredicate> PairTerms(const std::vector<attribute_id> &probe_keys, const std::vector<attribute_id> &build_keys,
+                                           bool components, const Predicate *residual) {
+  std::vector<ComparisonPredicate> terms;
+  for (std::size_t k = 0; components && k < probe_keys.size(); ++k) {
+    terms.push_back(ComparisonPredicate::Attributes(probe_keys[k], false, ComparisonID::kEqual, build_keys[k], true));
+  }
+  if (residual != nullptr) terms.insert(terms.end(), residual->conjuncts.begin(), residual->conjuncts.end());
+  return terms;
+}
+
+// Keeps the pairs under which every term holds: each term's operands gathered by the pair lists, compared, the bitmaps
+// chained through the terms like a conjunction, then one compaction of the pair lists.
+void FilterPairs(const ProbeSide &probe, const BuildSegments &build, const std::vector<ComparisonPredicate> &terms, JoinedPairs *pairs) {
+  if (terms.empty() || pairs->count == 0) return;
+  const std::int64_t m = pairs->count;
+  const std::size_t pair_bitmap_bytes = static_cast<std::size_t>((m + 63) / 64) * 8 + 8;
+  auto type_of = [&](attribute_id attr, bool on_build) -> const Type & { return (on_build ? build.relation : probe.relation).getAttributeType(attr); };
+  std::size_t widest = 8;
+  for (const ComparisonPredicate &term : terms) widest = std::max<std::size_t>(widest, type_of(term.attribute, term.on_build_side).width);
+  DeviceBuffer current(pair_bitmap_bytes), next(pair_bitmap_bytes), lhs(static_cast<std::size_t>(m) * widest + 8), rhs(static_cast<std::size_t>(m) * 8 + 8);
+  std::uint64_t *cur = static_cast<std::uint64_t *>(current.ptr), *nxt = static_cast<std::uint64_t *>(next.ptr);
+  auto gather_side = [&](attribute_id attr, bool on_build, void *dst) -> Type {
+    const Type t = type_of(attr, on_build);
+    if (on_build) {
+      build.gather(attr, t.width, pairs->build_tids->ptr, m, dst);
+    } else {
+      probe.gather(attr, t.width, pairs->probe_tids->ptr, m, dst);
+    }
+    return t;
+  };
+  const std::uint64_t *filter = nullptr;   // the pairs that passed the terms so far (nullptr: all)
+  for (const ComparisonPredicate &term : terms) {
+    if (IsLikeComparison(term.comparison)) CheckLikeTerm(term, type_of(term.attribute, term.on_build_side));
+    const Type t = gather_side(term.attribute, term.on_build_side, lhs.ptr);
+    if (term.rhs_attribute != kInvalidAttributeID) {
+      // (a run never gets here with such a term: executeRun vets the operands and hands the work order to the block form)
+      if (IsTextType(t.id)) throw ExecutionError("join predicate compares two string attributes (only string = literal is supported)", QSX_ERR_UNSUPPORTED);
+      const Type rt = gather_side(term.rhs_attribute, term.rhs_on_build_side, rhs.ptr);
+      if (rt.id != t.id) throw ExecutionError("join predicate compares attributes of different types", QSX_ERR_UNSUPPORTED);
+      CheckStatus(qsx_select_cmp_columns(t.id, lhs.ptr, rhs.ptr, m, static_cast<int>(term.comparison), filter, nxt, nullptr, CurrentStream()),
+                  "qsx_select_cmp_columns");
+    } else if (t.id == kChar) {
+      SelectCharTerm(term, lhs.ptr, t.width, m, filter, nxt, nullptr);
+    } else {
+      CheckStatus(qsx_select_cmp(t.id, lhs.ptr, m, static_cast<int>(term.comparison), &term.literal.v, filter, nxt, nullptr, CurrentStream()),
+                  "qsx_select_cmp");
+    }
+    std::swap(cur, nxt);
+    filter = cur;
+  }
+  CompactPairs(pairs, cur);
+}
+
+// found := the tuples among `about` (nullptr: among all `rows` tuples) that are NOT in found, in place: the complement of a
+// set of matched tuples must not bring back what a LIP filter rejected.
+void ComplementAmong(std::uint64_t *found, const std::uint64_t *about, std::int64_t rows) {
+  if (about != nullptr) {
+    CheckStatus(qsx_bitmap_combine(2, about, found, rows, found, CurrentStream()), "qsx_bitmap_combine");
+  } else {
+    CheckStatus(qsx_bitmap_combine(3, found, nullptr, rows, found, CurrentStream()), "qsx_bitmap_combine");
+  }
+}
+
+// Semi / anti output over a run: the probe tuples set in bitmaps[b] (at most `capacity`), projected on the probe attributes,
+// compacted into one output block; the null bits of nullable attributes follow by the output tuples' ids (base_tids[b] + row
+// when the run's tuple ids are word-aligned, else run-global row numbers).
+void EmitSelectedRun(const JoinOutput &to, const ProbeSide &probe, const std::uint64_t *const *bitmaps, const std::int32_t *base_tids,
+                     std::int64_t capacity, void *count_dev) {
+  bool nullable_output = false;
+  for (std::size_t i = 0; i < to.selection.size(); ++i) {
+    nullable_output = nullable_output || (!to.on_build[i] && probe.relation.getAttributeType(to.selection[i]).nullable);
+  }
+  const CompactedRun run = CompactRunInto(probe.blocks, probe.rows, to.selection, bitmaps, base_tids, capacity, nullable_output, to.destination, count_dev);
+  if (run.tids != nullptr) {
+    for (std::size_t i = 0; i < to.selection.size(); ++i) {
+      probe.gatherNulls(to.selection[i], run.tids->ptr, run.written, run.out->nullBitmap(static_cast<attribute_id>(i)));
+    }
+    CheckStatus(qsx_stream_synchronize(CurrentStream()), "qsx_stream_synchronize");
+  }
+  to.destination->returnBlock(run.out_id, run.written, to.partition);
+}
+
+// Inner / left outer output: the joined pairs first (Scalar::getAllValuesForJoin, :529-536), then — outer join — the
+// `unmatched` probe tuples of unmatched_tids with NULL build-side attributes (HashOuterJoinWorkOrder, :1026-1099:
+// result->fillWithNulls() is zero bytes here and the null bits of rows [matches, total)).  The null bits of an output attribute
+// are its source's at the joined rows and 1 under the padding.
+void EmitPairs(const JoinOutput &to, const ProbeSide &probe, const BuildSegments &build, const JoinedPairs &pairs,
+               const DeviceBuffer *unmatched_tids, std::int64_t unmatched) {
+  const std::int64_t matches = pairs.count, total = matches + unmatched;
+  block_id out_id;
+  BlockReference out = to.destination->getBlockForInsertion(total > 0 ? total : 1, &out_id);
+  // Row numbers of all `total` output rows per side, for the null bits: pairs first, then the unmatched probe tuples next to
+  // build tid -1 = NULL padding.  The pair lists themselves when nothing is unmatched; else made when an attribute first asks.
+  std::unique_ptr<DeviceBuffer> all_probe_tids, all_build_tids;
+  auto all_tids = [&](bool on_build) -> const void * {
+    std::unique_ptr<DeviceBuffer> &buf = on_build ? all_build_tids : all_probe_tids;
+    if (unmatched == 0) return on_build ? pairs.build_tids->ptr : pairs.probe_tids->ptr;
+    if (buf == nullptr) {
+      buf.reset(new DeviceBuffer(static_cast<std::size_t>(total) * 4 + 8));
+      char *tail = static_cast<char *>(buf->ptr) + static_cast<std::size_t>(matches) * 4;
+      CheckStatus(qsx_copy_on_device(buf->ptr, on_build ? pairs.build_tids->ptr : pairs.probe_tids->ptr,
+                                     static_cast<std::size_t>(matches) * 4, CurrentStream()), "qsx_copy_on_device");
+      if (on_build) {
+        CheckStatus(qsx_memset_device(tail, 0xFF, static_cast<std::size_t>(unmatched) * 4, CurrentStream()), "qsx_memset_device");
+      } else {
+        CheckStatus(qsx_copy_on_device(tail, unmatched_tids->ptr, static_cast<std::size_t>(unmatched) * 4, CurrentStream()),
+                    "qsx_copy_on_device");
+      }
+    }
+    return buf->ptr;
+  };
+  for (std::size_t i = 0; i < to.selection.size(); ++i) {
+    const attribute_id attr = to.selection[i];
+    const bool on_build = to.on_build[i];
+    const Type &t = (on_build ? build.relation : probe.relation).getAttributeType(attr);
+    char *dst = static_cast<char *>(out->stripe(static_cast<attribute_id>(i)));
+    char *tail = dst + static_cast<std::size_t>(matches) * t.width;
+    std::uint64_t *nulls = out->nullBitmap(static_cast<attribute_id>(i));
+    if (on_build) {
+      if (matches > 0) build.gather(attr, t.width, pairs.build_tids->ptr, matches, dst);
+      if (unmatched > 0) {
+        if (nulls == nullptr) throw ExecutionError("outer join output attribute taken from the build side must be nullable", QSX_ERR_INVALID_ARGUMENT);
+        CheckStatus(qsx_memset_device(tail, 0, static_cast<std::size_t>(unmatched) * t.width, CurrentStream()), "qsx_memset_device");
+      }
+      if (total > 0 && (t.nullable || unmatched > 0)) {
+        if (nulls == nullptr) throw ExecutionError("join output of a nullable attribute must be nullable", QSX_ERR_INVALID_ARGUMENT);
+        build.gatherNulls(attr, all_tids(true), total, nulls);
+      }
+    } else {
+      if (matches > 0) probe.gather(attr, t.width, pairs.probe_tids->ptr, matches, dst);
+      if (unmatched > 0) probe.gather(attr, t.width, unmatched_tids->ptr, unmatched, tail);
+      if (t.nullable && total > 0) probe.gatherNulls(attr, all_tids(false), total, nulls);
+    }
+  }
+  CheckStatus(qsx_stream_synchronize(CurrentStream()), "qsx_stream_synchronize");
+  to.destination->returnBlock(out_id, total, to.partition);   // output_destination_->bulkInsertTuples(&temp_result) (:539)
 }
 }  // namespace
 
@@ -165,120 +371,87 @@ void HashInnerJoinWorkOrder::execute() {
   for (block_id id : run_block_ids_) executeBlock(id);
 }
 
-// A run of probe blocks as one unit: one counting and one pair-emitting launch over all blocks (probe tuple ids are
-// run-global row numbers), then every output attribute is one segmented gather — the probe side from the run's own
-// stripes, the build side from the build relation's blocks — into ONE output block.
+// A run of probe blocks as one unit, into ONE output block.  The plan (executeBlock follows the same one):
+//   1. vet: a join type, a run size or an operand of a pair term that the run forms do not cover sends the whole work order
+//      to the block-by-block form (return false) before any device work is done for the run;
+//   2. the ProbeSide (tuple ids are run-global row numbers) and the key stripes;
+//   3. `about` = the tuples this work order is about (the LIP filters' survivors, or all), `lookup` = those of them that are
+//      looked up (no NULL in a key component);
+//   4. one of three routes:
+//      - the existence probe: a semi / anti join on an exact key without residual predicate — one probe for a bitmap per
+//        block, EmitSelectedRun;
+//      - the projecting probe: an inner join on an exact key without residual predicate whose outputs are plain values — the
+//        probe writes the output block itself; more matches than probe tuples and the work order takes the pair route;
+//      - the pair route: the pairs of the run -> FilterPairs (component equalities of a hashed key, the residual predicate) ->
+//        EmitSelectedRun for the probe tuples that kept / never had a pair (semi / anti), or EmitPairs (inner; outer with the
+//        probe tuples that have no pair added).
 bool HashInnerJoinWorkOrder::executeRun() {
   using JoinType = HashJoinOperator::JoinType;
-  const bool existence = join_type_ == JoinType::kLeftSemiJoin || join_type_ == JoinType::kLeftAntiJoin;
+  const bool anti = join_type_ == JoinType::kLeftAntiJoin;
+  const bool existence = join_type_ == JoinType::kLeftSemiJoin || anti;
   const bool outer = join_type_ == JoinType::kLeftOuterJoin;
+  // ---- 1. vet ----
   if (join_type_ != JoinType::kInnerJoin && !existence && !outer) return false;
   if (outer && residual_predicate_ != nullptr) return false;   // (HashOuterJoinWorkOrder takes none either)
-  // semi / anti with a residual predicate: the pairs of the run, the residual on them, then the probe tuples that kept (semi)
-  // or never had (anti) a pair — HashSemiJoinWorkOrder / HashAntiJoinWorkOrder::executeWithResidualPredicate (:680-793, :880-1000)
   int key_bits = 0;
   for (attribute_id a : join_key_attributes_) {   // (a CHAR(n <= 8) component travels as a LONG)
     key_bits += probe_relation_.getAttributeType(a).id == kChar ? 64 : probe_relation_.getAttributeType(a).width * 8;
   }
   const bool hashed_key = join_key_attributes_.size() > 1 && key_bits > 64;   // the fold is a hash: pairs need their components compared
-  // ... and so does a semi / anti join over a hashed composite key: an existence probe would count tuples whose key merely
-  // shares the fold with a build key (compositeKeyCollisionCheck, SeparateChainingHashTable.hpp:1046)
+  // semi / anti with a residual predicate: the pairs of the run, the residual on them, then the probe tuples that kept (semi)
+  // or never had (anti) a pair — HashSemiJoinWorkOrder / HashAntiJoinWorkOrder::executeWithResidualPredicate (:680-793, :880-1000)
+  // ... and so a semi / anti join over a hashed composite key: an existence probe would count tuples whose key merely
+  // shares the fold with a build key
   const bool existence_by_pairs = existence && (residual_predicate_ != nullptr || hashed_key);
-  std::vector<BlockReference> blocks;
-  std::vector<std::int64_t> rows, first_rows;
-  std::int64_t total_rows = 0;
+  // The run form gathers the operands of a pair term with widths of 1 / 2 / 4 / 8 bytes and compares numeric types (a CHAR(n)
+  // attribute only against a literal: qsx_select_cmp_char): no nullable, VARCHAR or CHAR-vs-attribute operand.
+  auto operand_ok = [&](attribute_id attr, bool on_build, bool against_literal) {
+    const Type &t = (on_build ? build_relation_ : probe_relation_).getAttributeType(attr);
+    return !t.nullable && t.id != kVarChar && (t.id != kChar || against_literal);
+  };
+  for (const ComparisonPredicate &term : PairTerms(join_key_attributes_, build_key_attributes_, hashed_key, residual_predicate_)) {
+    const bool literal = term.rhs_attribute == kInvalidAttributeID;
+    if (!operand_ok(term.attribute, term.on_build_side, literal)) return false;
+    if (!literal && !operand_ok(term.rhs_attribute, term.rhs_on_build_side, false)) return false;
+  }
+  // ---- 2. the probe side and its keys ----
+  ProbeSide probe(probe_relation_, /*is_run=*/true);
   bool any_null_key = false;   // some block holds NULLs in a key attribute: those tuples are not looked up
   for (block_id id : run_block_ids_) {
-    blocks.push_back(storage_manager_->getBlock(id));
-    const StorageBlock &b = *blocks.back();
-    for (attribute_id a : join_key_attributes_) any_null_key = any_null_key || b.nullBitmap(a) != nullptr;   // (compressed key: stripe() decodes once)
-    rows.push_back(b.numTuples());
-    first_rows.push_back(total_rows);
-    total_rows += b.numTuples();
-    // (the pairs of a semi / anti join end up as ONE bitmap over the run's tuple ids: every block starts at a word boundary,
-    // so that its part of the bitmap is the bitmap of the block)
-    if (existence_by_pairs || outer) total_rows = (total_rows + 63) / 64 * 64;
+    BlockReference b = storage_manager_->getBlock(id);
+    for (attribute_id a : join_key_attributes_) any_null_key = any_null_key || b->nullBitmap(a) != nullptr;   // (compressed key: stripe() decodes once)
+    probe.add(std::move(b), /*word_aligned=*/existence_by_pairs || outer);
   }
+  const std::vector<BlockReference> &blocks = probe.blocks;
+  const std::vector<std::int64_t> &rows = probe.rows;
+  const std::int64_t total_rows = probe.total_rows;
   if (total_rows > INT32_MAX || blocks.size() > 16384) return false;
   const std::int64_t nb = static_cast<std::int64_t>(blocks.size());
-  // The terms evaluated on the pair list (component equalities of a hashed composite key, residual conjuncts): the run form
-  // gathers their operands with widths of 1 / 2 / 4 / 8 bytes and compares numeric types — a nullable or CHAR(n) operand
-  // sends the whole work order to the block-by-block form BEFORE any device work is done for the run.
-  {
-    auto operand_ok = [&](attribute_id attr, bool on_build, bool against_literal) {
-      const Type &t = (on_build ? build_relation_ : probe_relation_).getAttributeType(attr);
-      // (a CHAR(n) attribute against a literal is compared by qsx_select_cmp_char; attribute against attribute is numeric)
-      return !t.nullable && t.id != kVarChar && (t.id != kChar || against_literal);
-    };
-    if (hashed_key) {
-      for (std::size_t k = 0; k < join_key_attributes_.size(); ++k) {
-        if (!operand_ok(join_key_attributes_[k], false, false) || !operand_ok(build_key_attributes_[k], true, false)) return false;
-      }
-    }
-    if (residual_predicate_ != nullptr) {
-      for (const ComparisonPredicate &term : residual_predicate_->conjuncts) {
-        const bool literal = term.rhs_attribute == kInvalidAttributeID;
-        if (!operand_ok(term.attribute, term.on_build_side, literal)) return false;
-        if (!literal && !operand_ok(term.rhs_attribute, term.rhs_on_build_side, false)) return false;
-      }
-    }
-  }
   const RunJoinKeys run_keys(blocks, join_key_attributes_, rows);   // composite key: one launch packs the run's keys
   const std::vector<const void *> &keys = run_keys.ptr;
+  // ---- 3. about and lookup ----
   // existence_map of the LIPFilterAdaptiveProber (:462-470): the probe tuples this work order looks up
-  struct OwnedStorage {
-    void *ptr = nullptr;
-    ~OwnedStorage() { qsx_device_free(ptr); }
-  } lip_storage;
+  DeviceAllocation lip_storage;
   std::vector<const std::uint64_t *> lip_bitmaps;
   if (lip_filter_adaptive_prober_ != nullptr && !lip_filter_adaptive_prober_->filterBlocks(blocks, &lip_storage.ptr, &lip_bitmaps)) return false;
-  // `about` = the tuples this work order is about (the LIP filter's survivors, or all); `lookup` = those of them that are
-  // looked up: a probe tuple with a NULL key component matches nothing (check_for_null_keys, HashTable.hpp:2158-2160,
-  // 1855-1865) — out of an inner / semi join, NULL-padded by an outer join, KEPT by an anti join.  Blocks without NULLs in
-  // their key attributes (no bitmap) cost nothing here.
-  const std::uint64_t *const *about = lip_bitmaps.empty() ? nullptr : lip_bitmaps.data();
+  // A probe tuple with a NULL key component matches nothing (check_for_null_keys, HashTable.hpp:2158-2160, 1855-1865) — out
+  // of an inner / semi join, NULL-padded by an outer join, KEPT by an anti join.  Blocks without NULLs in their key
+  // attributes (no bitmap) cost nothing here.
+  std::vector<const std::uint64_t *> about(blocks.size(), nullptr);
+  if (!lip_bitmaps.empty()) about = lip_bitmaps;
   std::vector<std::unique_ptr<DeviceBuffer>> not_null_storage;
   std::vector<const std::uint64_t *> lookup_bitmaps;
   if (any_null_key) {
     for (std::size_t b = 0; b < blocks.size(); ++b) {
-      const std::uint64_t *in = about != nullptr ? about[b] : nullptr;
-      std::unique_ptr<DeviceBuffer> not_null = NotNullFilter(*blocks[b], join_key_attributes_, in);
-      lookup_bitmaps.push_back(not_null != nullptr ? static_cast<const std::uint64_t *>(not_null->ptr) : in);
+      std::unique_ptr<DeviceBuffer> not_null = NotNullFilter(*blocks[b], join_key_attributes_, about[b]);
+      lookup_bitmaps.push_back(not_null != nullptr ? static_cast<const std::uint64_t *>(not_null->ptr) : about[b]);
       not_null_storage.push_back(std::move(not_null));
     }
   }
-  const std::uint64_t *const *lookup = any_null_key ? lookup_bitmaps.data() : about;
-  // nullable probe-side output attributes: their null bits follow the output tuples (qsx_bitmap_gather_segmented over the
-  // blocks' null bitmaps, by the same tuple ids that gather the values)
-  auto gather_probe_nulls = [&](std::size_t i, const void *tids, std::int64_t n, BlockReference &out, std::int64_t out_first_bit) {
-    const Type &t = probe_relation_.getAttributeType(selection_[i]);
-    if (!t.nullable || n == 0) return;
-    bool any = false;
-    std::vector<const std::uint64_t *> segs(blocks.size());
-    for (std::size_t b = 0; b < blocks.size(); ++b) {
-      segs[b] = blocks[b]->nullBitmap(selection_[i]);
-      any = any || segs[b] != nullptr;
-    }
-    std::uint64_t *nulls = out->nullBitmap(static_cast<attribute_id>(i));
-    if (nulls == nullptr) throw ExecutionError("join output of a nullable attribute must be nullable", QSX_ERR_INVALID_ARGUMENT);
-    if (!any) return;   // (the output block's bitmaps start zeroed)
-    if ((out_first_bit & 63) != 0) throw ExecutionError("join output null bits: unaligned tail", QSX_ERR_UNSUPPORTED);
-    // empty blocks share their first row with the next one: the gather wants strictly increasing segment starts
-    std::vector<const std::uint64_t *> used_segs;
-    std::vector<std::int64_t> used_first;
-    for (std::size_t b = 0; b < blocks.size(); ++b) {
-      if (rows[b] == 0) continue;
-      used_segs.push_back(segs[b]);
-      used_first.push_back(first_rows[b]);
-    }
-    CheckStatus(qsx_bitmap_gather_segmented(static_cast<int>(used_segs.size()), used_segs.data(), used_first.data(), static_cast<const std::int32_t *>(tids), n,
-                                            nulls + out_first_bit / 64, CurrentStream()), "qsx_bitmap_gather_segmented");
-  };
-  bool nullable_probe_output = false;
-  for (std::size_t i = 0; i < selection_.size(); ++i) {
-    nullable_probe_output = nullable_probe_output || (!is_selection_on_build_[i] && probe_relation_.getAttributeType(selection_[i]).nullable);
-  }
+  const std::uint64_t *const *lookup = any_null_key ? lookup_bitmaps.data() : lip_bitmaps.empty() ? nullptr : lip_bitmaps.data();
+  const JoinOutput to{selection_, is_selection_on_build_, output_destination_, getPartitionId()};
   DeviceBuffer count(8);
+  // ---- 4a. the existence probe ----
   if (existence && !existence_by_pairs) {
     // HashSemiJoinWorkOrder / HashAntiJoinWorkOrder without residual (:795-816, :860-877): the probe tuples with / without a
     // match, projected on the probe attributes — one existence probe and one compaction over the run
@@ -291,9 +464,8 @@ bool HashInnerJoinWorkOrder::executeRun() {
       bitmaps[b] = static_cast<std::uint64_t *>(bitmap_storage.ptr) + at;
       at += static_cast<std::size_t>((rows[b] + 63) / 64) + 1;
     }
-    const bool anti = join_type_ == JoinType::kLeftAntiJoin;
-    // (an anti join over NULL keys: the tuples FOUND among those looked up, then "about AND NOT found" block by block — a
-    // tuple that was not looked up was not found and stays)
+    // (an anti join over NULL keys: the tuples FOUND among those looked up, then their complement among `about` block by
+    // block — a tuple that was not looked up was not found and stays)
     const bool anti_by_complement = anti && any_null_key;
     CheckStatus(qsx_join_probe_exists_blocks_coded(hash_table_, nb, rows.data(), keys.data(), run_keys.coding(), lookup,
                                                    anti && !anti_by_complement ? 1 : 0, bitmaps.data(),
@@ -304,40 +476,14 @@ bool HashInnerJoinWorkOrder::executeRun() {
       selected = 0;
       for (std::size_t b = 0; b < blocks.size(); ++b) {
         selected += rows[b];
-        if (rows[b] == 0) continue;
-        if (about != nullptr && about[b] != nullptr) {
-          CheckStatus(qsx_bitmap_combine(2, about[b], bitmaps[b], rows[b], bitmaps[b], CurrentStream()), "qsx_bitmap_combine");
-        } else {
-          CheckStatus(qsx_bitmap_combine(3, bitmaps[b], nullptr, rows[b], bitmaps[b], CurrentStream()), "qsx_bitmap_combine");
-        }
+        if (rows[b] > 0) ComplementAmong(bitmaps[b], about[b], rows[b]);
       }
     }
-    block_id out_id;
-    BlockReference out = output_destination_->getBlockForInsertion(selected > 0 ? selected : 1, &out_id);
-    std::vector<const void *> src(blocks.size() * selection_.size());
-    std::vector<void *> dst;
-    std::vector<std::int32_t> widths;
-    for (std::size_t i = 0; i < selection_.size(); ++i) {
-      dst.push_back(out->stripe(static_cast<attribute_id>(i)));
-      widths.push_back(probe_relation_.getAttributeType(selection_[i]).width);
-      for (std::size_t b = 0; b < blocks.size(); ++b) src[b * selection_.size() + i] = blocks[b]->stripe(selection_[i]);
-    }
-    const std::size_t ws_bytes = qsx_compact_blocks_workspace_bytes(nb, rows.data());
-    DeviceBuffer ws(ws_bytes + 8);
-    std::unique_ptr<DeviceBuffer> out_tids;   // run-global row number of every output tuple (nullable outputs: their null bits)
-    if (nullable_probe_output) out_tids.reset(new DeviceBuffer(static_cast<std::size_t>(selected > 0 ? selected : 1) * 4 + 8));
-    CheckStatus(qsx_compact_gather_blocks(static_cast<int>(selection_.size()), widths.data(), nb, rows.data(), src.data(),
-                                          reinterpret_cast<const std::uint64_t *const *>(bitmaps.data()), nullptr, dst.data(),
-                                          out_tids != nullptr ? static_cast<std::int32_t *>(out_tids->ptr) : nullptr,
-                                          static_cast<std::int64_t *>(count.ptr), ws.ptr, ws_bytes, CurrentStream()),
-                "qsx_compact_gather_blocks");
-    const std::int64_t written = ReadCount(count.ptr);
-    for (std::size_t i = 0; i < selection_.size() && out_tids != nullptr; ++i) gather_probe_nulls(i, out_tids->ptr, written, out, 0);
-    if (out_tids != nullptr) CheckStatus(qsx_stream_synchronize(CurrentStream()), "qsx_stream_synchronize");
-    output_destination_->returnBlock(out_id, written, getPartitionId());
+    EmitSelectedRun(to, probe, reinterpret_cast<const std::uint64_t *const *>(bitmaps.data()), nullptr, selected, count.ptr);
     return true;
   }
   BuildSegments build(build_relation_, storage_manager_);
+  // ---- 4b. the projecting probe (only the run form has it) ----
   // Nothing is evaluated on the pairs (an exact key, no residual predicate) and every output attribute is a plain value of
   // 1 / 2 / 4 / 8 bytes: the probe writes the output tuples itself (qsx_join_probe_project_blocks) into a block with room for
   // one match per probe tuple.  More matches than that (duplicate build keys) and the work order takes the pair list below.
@@ -398,263 +544,95 @@ bool HashInnerJoinWorkOrder::executeRun() {
     out = BlockReference();
     storage_manager_->deleteBlockOrBlobFile(out_id);   // never returned to the destination: nobody else knows the block
   }
-  // No counting pass: the pair lists get room for one match per probe tuple — what a foreign-key probe of a primary-key
-  // build side produces at most (the reference sizes from the same uniqueness fact, impliesUniqueAttributes).  The probe
-  // counts every match it finds, also those that did not fit: a build side with duplicate keys makes this work order probe
-  // once more with the exact capacity.
+  // ---- 4c. the pair route ----
+  // (run form only) No counting pass: the pair lists get room for one match per probe tuple — what a foreign-key probe of a
+  // primary-key build side produces at most (the reference sizes from the same uniqueness fact, impliesUniqueAttributes).
+  // The probe counts every match it finds, also those that did not fit: a build side with duplicate keys makes this work
+  // order probe once more with the exact capacity.  (The block form counts first.)
   JoinedPairs pairs;
   std::int64_t room = total_rows > 0 ? total_rows : 1;
-  std::vector<std::int32_t> base_tids;   // semi / anti by pairs: the word-aligned first tuple id of every block (first_rows)
-  if (existence_by_pairs || outer) base_tids.assign(first_rows.begin(), first_rows.end());
+  std::vector<std::int32_t> base_tids;   // tuple ids that end in a bitmap: the word-aligned first tuple id of every block (first_rows)
+  if (existence_by_pairs || outer) base_tids.assign(probe.first_rows.begin(), probe.first_rows.end());
   for (int attempt = 0; attempt < 2; ++attempt) {
     pairs.probe_tids.reset(new DeviceBuffer(static_cast<std::size_t>(room) * 4 + 8));
     pairs.build_tids.reset(new DeviceBuffer(static_cast<std::size_t>(room) * 4 + 8));
     CheckStatus(qsx_join_probe_blocks_coded(hash_table_, nb, rows.data(), keys.data(), run_keys.coding(),
                                             base_tids.empty() ? nullptr : base_tids.data(), lookup,
                                             static_cast<std::int32_t *>(pairs.probe_tids->ptr),
-                                      static_cast<std::int32_t *>(pairs.build_tids->ptr), room, static_cast<std::int64_t *>(count.ptr),
-                                      CurrentStream()), "qsx_join_probe_blocks");
+                                            static_cast<std::int32_t *>(pairs.build_tids->ptr), room, static_cast<std::int64_t *>(count.ptr),
+                                            CurrentStream()), "qsx_join_probe_blocks");
     pairs.count = ReadCount(count.ptr);
     if (pairs.count <= room) break;
     if (attempt == 1) throw ExecutionError("HashJoinOperator: the match count changed between two probes of one run", QSX_ERR_CAPACITY);
     room = pairs.count;
   }
-  std::vector<const void *> segments(blocks.size());
-  std::vector<ComparisonPredicate> terms;
-  if (!run_keys.exact) {   // compositeKeyCollisionCheck (SeparateChainingHashTable.hpp:1046): equal folds, equal components?
-    for (std::size_t k = 0; k < join_key_attributes_.size(); ++k) {
-      terms.push_back(ComparisonPredicate::Attributes(join_key_attributes_[k], false, ComparisonID::kEqual, build_key_attributes_[k], true));
-    }
+  FilterPairs(probe, build, PairTerms(join_key_attributes_, build_key_attributes_, !run_keys.exact, residual_predicate_), &pairs);
+  if (!existence_by_pairs && !outer) {
+    EmitPairs(to, probe, build, pairs, nullptr, 0);
+    return true;
   }
-  if (residual_predicate_ != nullptr) terms.insert(terms.end(), residual_predicate_->conjuncts.begin(), residual_predicate_->conjuncts.end());
-  if (!terms.empty() && pairs.count > 0) {
-    // matchesForJoinedTuples (:510-524) on the pairs of the run: each term's operands gathered by the pair lists (the probe
-    // side through the run's own stripes), compared, chained through the filter bitmap like a conjunction
-    const std::int64_t m = pairs.count;
-    const std::size_t pair_bitmap_bytes = static_cast<std::size_t>((m + 63) / 64) * 8 + 8;
-    std::size_t widest = 8;
-    for (const ComparisonPredicate &term : terms) {
-      widest = std::max<std::size_t>(widest, (term.on_build_side ? build_relation_ : probe_relation_).getAttributeType(term.attribute).width);
-    }
-    DeviceBuffer current(pair_bitmap_bytes), next(pair_bitmap_bytes), lhs(static_cast<std::size_t>(m) * widest + 8), rhs(static_cast<std::size_t>(m) * 8 + 8);
-    void *cur = current.ptr, *nxt = next.ptr;
-    bool first = true;
-    auto gather_side = [&](attribute_id attr, bool on_build, void *dst) -> Type {
-      const Type t = (on_build ? build_relation_ : probe_relation_).getAttributeType(attr);
-      if (on_build) {
-        build.gather(attr, t.width, pairs.build_tids->ptr, m, dst);
-      } else {
-        for (std::size_t b = 0; b < blocks.size(); ++b) segments[b] = blocks[b]->stripe(attr);
-        CheckStatus(qsx_gather_segmented(t.width, static_cast<int>(segments.size()), segments.data(), first_rows.data(),
-                                         static_cast<const std::int32_t *>(pairs.probe_tids->ptr), m, dst, CurrentStream()),
-                    "qsx_gather_segmented");
-      }
-      return t;
-    };
-    for (const ComparisonPredicate &term : terms) {
-      if (IsLikeComparison(term.comparison)) CheckLikeTerm(term, (term.on_build_side ? build_relation_ : probe_relation_).getAttributeType(term.attribute));
-      const Type t = gather_side(term.attribute, term.on_build_side, lhs.ptr);   // (operand types were vetted above)
-      if (term.rhs_attribute != kInvalidAttributeID) {
-        const Type rt = gather_side(term.rhs_attribute, term.rhs_on_build_side, rhs.ptr);
-        if (rt.id != t.id) throw ExecutionError("join predicate compares attributes of different types", QSX_ERR_UNSUPPORTED);
-        CheckStatus(qsx_select_cmp_columns(t.id, lhs.ptr, rhs.ptr, m, static_cast<int>(term.comparison),
-                                           first ? nullptr : static_cast<const std::uint64_t *>(cur), static_cast<std::uint64_t *>(nxt), nullptr,
-                                           CurrentStream()), "qsx_select_cmp_columns");
-      } else if (t.id == kChar) {
-        SelectCharTerm(term, lhs.ptr, t.width, m, first ? nullptr : static_cast<const std::uint64_t *>(cur), static_cast<std::uint64_t *>(nxt), nullptr);
-      } else {
-        CheckStatus(qsx_select_cmp(t.id, lhs.ptr, m, static_cast<int>(term.comparison), &term.literal.v,
-                                   first ? nullptr : static_cast<const std::uint64_t *>(cur), static_cast<std::uint64_t *>(nxt), nullptr,
-                                   CurrentStream()), "qsx_select_cmp");
-      }
-      std::swap(cur, nxt);
-      first = false;
-    }
-    if (!first) CompactPairs(&pairs, cur);
+  // semi / anti by pairs, outer: the probe tuples that kept a pair as ONE bitmap over the run's (word-aligned) tuple ids, then
+  // (anti, outer) its complement among `about` block by block — the complement of a block's part ends at the block's last
+  // tuple.  (`about`, not `lookup`: a tuple with a NULL key is kept by an anti join and NULL-padded by an outer join.)
+  const std::size_t words = static_cast<std::size_t>(total_rows / 64) + 1;
+  DeviceBuffer bitmap(words * 8 + 8);
+  CheckStatus(qsx_tids_to_bitmap(static_cast<const std::int32_t *>(pairs.probe_tids->ptr), pairs.count, 0, total_rows,
+                                 static_cast<std::uint64_t *>(bitmap.ptr), CurrentStream()), "qsx_tids_to_bitmap");
+  std::vector<const std::uint64_t *> bitmaps(blocks.size());
+  for (std::size_t b = 0; b < blocks.size(); ++b) {
+    std::uint64_t *part = static_cast<std::uint64_t *>(bitmap.ptr) + probe.first_rows[b] / 64;
+    if (join_type_ != JoinType::kLeftSemiJoin && rows[b] > 0) ComplementAmong(part, about[b], rows[b]);
+    bitmaps[b] = part;
   }
   if (existence_by_pairs) {
-    // the probe tuples that kept a pair, as one bitmap over the run's (word-aligned) tuple ids; anti: its complement, block by
-    // block (the complement of a block's part ends at the block's last tuple); then one compaction over the run
-    const std::size_t words = static_cast<std::size_t>(total_rows / 64) + 1;
-    DeviceBuffer bitmap(words * 8 + 8);
-    CheckStatus(qsx_tids_to_bitmap(static_cast<const std::int32_t *>(pairs.probe_tids->ptr), pairs.count, 0, total_rows,
-                                   static_cast<std::uint64_t *>(bitmap.ptr), CurrentStream()), "qsx_tids_to_bitmap");
-    std::vector<std::uint64_t *> bitmaps(blocks.size());
     std::int64_t upper = 0;   // tuples the compaction can select at most
-    for (std::size_t b = 0; b < blocks.size(); ++b) {
-      bitmaps[b] = static_cast<std::uint64_t *>(bitmap.ptr) + first_rows[b] / 64;
-      if (join_type_ == JoinType::kLeftAntiJoin && rows[b] > 0) {
-        // the tuples WITHOUT a surviving pair — among those this work order is about: what a LIP filter rejected must not
-        // come back through the complement
-        if (about != nullptr && about[b] != nullptr) {
-          CheckStatus(qsx_bitmap_combine(2, about[b], bitmaps[b], rows[b], bitmaps[b], CurrentStream()), "qsx_bitmap_combine");
-        } else {
-          CheckStatus(qsx_bitmap_combine(3, bitmaps[b], nullptr, rows[b], bitmaps[b], CurrentStream()), "qsx_bitmap_combine");
-        }
-      }
-      upper += rows[b];
-    }
-    if (join_type_ == JoinType::kLeftSemiJoin) upper = std::min<std::int64_t>(upper, pairs.count);
-    block_id out_id;
-    BlockReference out = output_destination_->getBlockForInsertion(upper > 0 ? upper : 1, &out_id);
-    std::vector<const void *> src(blocks.size() * selection_.size());
-    std::vector<void *> dst;
-    std::vector<std::int32_t> widths;
-    for (std::size_t i = 0; i < selection_.size(); ++i) {
-      dst.push_back(out->stripe(static_cast<attribute_id>(i)));
-      widths.push_back(probe_relation_.getAttributeType(selection_[i]).width);
-      for (std::size_t b = 0; b < blocks.size(); ++b) src[b * selection_.size() + i] = blocks[b]->stripe(selection_[i]);
-    }
-    const std::size_t ws_bytes = qsx_compact_blocks_workspace_bytes(nb, rows.data());
-    DeviceBuffer ws(ws_bytes + 8);
-    std::unique_ptr<DeviceBuffer> out_tids;   // the (word-aligned, like the bitmap) tuple id of every output tuple
-    if (nullable_probe_output) out_tids.reset(new DeviceBuffer(static_cast<std::size_t>(upper > 0 ? upper : 1) * 4 + 8));
-    CheckStatus(qsx_compact_gather_blocks(static_cast<int>(selection_.size()), widths.data(), nb, rows.data(), src.data(),
-                                          reinterpret_cast<const std::uint64_t *const *>(bitmaps.data()), out_tids != nullptr ? base_tids.data() : nullptr,
-                                          dst.data(), out_tids != nullptr ? static_cast<std::int32_t *>(out_tids->ptr) : nullptr,
-                                          static_cast<std::int64_t *>(count.ptr), ws.ptr, ws_bytes, CurrentStream()),
-                "qsx_compact_gather_blocks");
-    const std::int64_t written = ReadCount(count.ptr);
-    for (std::size_t i = 0; i < selection_.size() && out_tids != nullptr; ++i) gather_probe_nulls(i, out_tids->ptr, written, out, 0);
-    if (out_tids != nullptr) CheckStatus(qsx_stream_synchronize(CurrentStream()), "qsx_stream_synchronize");
-    output_destination_->returnBlock(out_id, written, getPartitionId());
+    for (std::int64_t r : rows) upper += r;
+    if (!anti) upper = std::min<std::int64_t>(upper, pairs.count);
+    EmitSelectedRun(to, probe, bitmaps.data(), base_tids.data(), upper, count.ptr);
     return true;
   }
-  if (outer) {
-    // HashOuterJoinWorkOrder (:1026-1099) over the run: the matched pairs, then the probe tuples without one (the complement of
-    // the matched tuples' bitmap, block by block so that it ends at each block's last tuple, AND the LIP filter's survivors)
-    // with NULL build-side attributes
-    const std::int64_t matches = pairs.count;
-    const std::size_t words = static_cast<std::size_t>(total_rows / 64) + 1;
-    DeviceBuffer bitmap(words * 8 + 8);
-    CheckStatus(qsx_tids_to_bitmap(static_cast<const std::int32_t *>(pairs.probe_tids->ptr), matches, 0, total_rows,
-                                   static_cast<std::uint64_t *>(bitmap.ptr), CurrentStream()), "qsx_tids_to_bitmap");
-    for (std::size_t b = 0; b < blocks.size(); ++b) {
-      if (rows[b] == 0) continue;
-      std::uint64_t *part = static_cast<std::uint64_t *>(bitmap.ptr) + first_rows[b] / 64;
-      CheckStatus(qsx_bitmap_combine(3, part, nullptr, rows[b], part, CurrentStream()), "qsx_bitmap_combine");
-      if (about != nullptr && about[b] != nullptr) {   // (NOT `lookup`: a tuple with a NULL key is NULL-padded, not dropped)
-        CheckStatus(qsx_bitmap_combine(0, part, about[b], rows[b], part, CurrentStream()), "qsx_bitmap_combine");
-      }
-    }
-    DeviceBuffer unmatched_tids(static_cast<std::size_t>(total_rows) * 4 + 8);
-    const std::size_t ws_bytes = qsx_compact_workspace_bytes(total_rows);
-    DeviceBuffer ws(ws_bytes + 8);
-    CheckStatus(qsx_bitmap_to_tids(static_cast<const std::uint64_t *>(bitmap.ptr), total_rows, 0, static_cast<std::int32_t *>(unmatched_tids.ptr),
-                                   static_cast<std::int64_t *>(count.ptr), ws.ptr, ws_bytes, CurrentStream()), "qsx_bitmap_to_tids");
-    const std::int64_t unmatched = ReadCount(count.ptr);
-    const std::int64_t total = matches + unmatched;
-    block_id out_id;
-    BlockReference out = output_destination_->getBlockForInsertion(total > 0 ? total : 1, &out_id);
-    std::unique_ptr<DeviceBuffer> padded_build_tids;   // the pairs' build tuple ids, then -1 for every unmatched probe tuple
-    std::unique_ptr<DeviceBuffer> all_probe_tids;      // the pairs' probe tuple ids, then the unmatched ones: the output's order
-    if (nullable_probe_output && total > 0) {
-      all_probe_tids.reset(new DeviceBuffer(static_cast<std::size_t>(total) * 4 + 8));
-      if (matches > 0) {
-        CheckStatus(qsx_copy_on_device(all_probe_tids->ptr, pairs.probe_tids->ptr, static_cast<std::size_t>(matches) * 4, CurrentStream()), "qsx_copy_on_device");
-      }
-      if (unmatched > 0) {
-        CheckStatus(qsx_copy_on_device(static_cast<char *>(all_probe_tids->ptr) + static_cast<std::size_t>(matches) * 4, unmatched_tids.ptr,
-                                       static_cast<std::size_t>(unmatched) * 4, CurrentStream()), "qsx_copy_on_device");
-      }
-    }
-    for (std::size_t i = 0; i < selection_.size(); ++i) {
-      char *dst = static_cast<char *>(out->stripe(static_cast<attribute_id>(i)));
-      const bool on_build = is_selection_on_build_[i];
-      const Type &t = (on_build ? build_relation_ : probe_relation_).getAttributeType(selection_[i]);
-      char *tail = dst + static_cast<std::size_t>(matches) * t.width;
-      if (on_build) {
-        std::uint64_t *nulls = out->nullBitmap(static_cast<attribute_id>(i));
-        if (nulls == nullptr) throw ExecutionError("outer join output attribute taken from the build side must be nullable", QSX_ERR_INVALID_ARGUMENT);
-        if (matches > 0) build.gather(selection_[i], t.width, pairs.build_tids->ptr, matches, dst);
-        if (unmatched > 0) CheckStatus(qsx_memset_device(tail, 0, static_cast<std::size_t>(unmatched) * t.width, CurrentStream()), "qsx_memset_device");
-        if (total > 0) {
-          if (padded_build_tids == nullptr) {
-            padded_build_tids.reset(new DeviceBuffer(static_cast<std::size_t>(total) * 4 + 8));
-            if (matches > 0) {
-              CheckStatus(qsx_copy_on_device(padded_build_tids->ptr, pairs.build_tids->ptr, static_cast<std::size_t>(matches) * 4, CurrentStream()),
-                          "qsx_copy_on_device");
-            }
-            if (unmatched > 0) {
-              CheckStatus(qsx_memset_device(static_cast<char *>(padded_build_tids->ptr) + static_cast<std::size_t>(matches) * 4, 0xFF,
-                                            static_cast<std::size_t>(unmatched) * 4, CurrentStream()), "qsx_memset_device");
-            }
-          }
-          build.gatherNulls(selection_[i], padded_build_tids->ptr, total, nulls);
-        }
-      } else {
-        for (std::size_t b = 0; b < blocks.size(); ++b) segments[b] = blocks[b]->stripe(selection_[i]);
-        if (matches > 0) {
-          CheckStatus(qsx_gather_segmented(t.width, static_cast<int>(segments.size()), segments.data(), first_rows.data(),
-                                           static_cast<const std::int32_t *>(pairs.probe_tids->ptr), matches, dst, CurrentStream()),
-                      "qsx_gather_segmented");
-        }
-        if (unmatched > 0) {
-          CheckStatus(qsx_gather_segmented(t.width, static_cast<int>(segments.size()), segments.data(), first_rows.data(),
-                                           static_cast<const std::int32_t *>(unmatched_tids.ptr), unmatched, tail, CurrentStream()),
-                      "qsx_gather_segmented");
-        }
-        if (all_probe_tids != nullptr) gather_probe_nulls(i, all_probe_tids->ptr, total, out, 0);
-      }
-    }
-    CheckStatus(qsx_stream_synchronize(CurrentStream()), "qsx_stream_synchronize");
-    output_destination_->returnBlock(out_id, total, getPartitionId());
-    return true;
-  }
-  const std::int64_t matches = pairs.count;
-  DeviceBuffer &probe_tids = *pairs.probe_tids, &build_tids = *pairs.build_tids;
-  block_id out_id;
-  BlockReference out = output_destination_->getBlockForInsertion(matches > 0 ? matches : 1, &out_id);
-  for (std::size_t i = 0; i < selection_.size(); ++i) {
-    void *dst = out->stripe(static_cast<attribute_id>(i));
-    const bool on_build = is_selection_on_build_[i];
-    const Type &t = (on_build ? build_relation_ : probe_relation_).getAttributeType(selection_[i]);
-    if (on_build) {
-      build.gather(selection_[i], t.width, build_tids.ptr, matches, dst);
-      if (t.nullable && matches > 0) {
-        std::uint64_t *nulls = out->nullBitmap(static_cast<attribute_id>(i));
-        if (nulls == nullptr) throw ExecutionError("join output of a nullable attribute must be nullable", QSX_ERR_INVALID_ARGUMENT);
-        build.gatherNulls(selection_[i], build_tids.ptr, matches, nulls);
-      }
-    } else {
-      for (std::size_t b = 0; b < blocks.size(); ++b) segments[b] = blocks[b]->stripe(selection_[i]);
-      CheckStatus(qsx_gather_segmented(t.width, static_cast<int>(segments.size()), segments.data(), first_rows.data(),
-                                       static_cast<const std::int32_t *>(probe_tids.ptr), matches, dst, CurrentStream()),
-                  "qsx_gather_segmented");
-      gather_probe_nulls(i, probe_tids.ptr, matches, out, 0);
-    }
-  }
-  CheckStatus(qsx_stream_synchronize(CurrentStream()), "qsx_stream_synchronize");
-  output_destination_->returnBlock(out_id, matches, getPartitionId());
+  // HashOuterJoinWorkOrder (:1026-1099) over the run: the matched pairs, then the probe tuples without one
+  DeviceBuffer unmatched_tids(static_cast<std::size_t>(total_rows) * 4 + 8);
+  const std::size_t ws_bytes = qsx_compact_workspace_bytes(total_rows);
+  DeviceBuffer ws(ws_bytes + 8);
+  CheckStatus(qsx_bitmap_to_tids(static_cast<const std::uint64_t *>(bitmap.ptr), total_rows, 0, static_cast<std::int32_t *>(unmatched_tids.ptr),
+                                 static_cast<std::int64_t *>(count.ptr), ws.ptr, ws_bytes, CurrentStream()), "qsx_bitmap_to_tids");
+  const std::int64_t unmatched = ReadCount(count.ptr);
+  EmitPairs(to, probe, build, pairs, &unmatched_tids, unmatched);
   return true;
 }
 
+// One probe block: the plan of executeRun with the single-block entry points, without the projecting probe.
 void HashInnerJoinWorkOrder::executeBlock(block_id probe_block_id) {
   using JoinType = HashJoinOperator::JoinType;
-  BlockReference probe = storage_manager_->getBlock(probe_block_id);
-  const std::int64_t n = probe->numTuples();
-  JoinKeys keys(*probe, join_key_attributes_);
+  const bool anti = join_type_ == JoinType::kLeftAntiJoin;
+  const bool existence = join_type_ == JoinType::kLeftSemiJoin || anti;
+  // ---- the probe side and its keys ----
+  ProbeSide probe(probe_relation_, /*is_run=*/false);
+  probe.add(storage_manager_->getBlock(probe_block_id), /*word_aligned=*/false);
+  const StorageBlock &block = *probe.blocks.front();
+  const std::int64_t n = probe.total_rows;
+  JoinKeys keys(block, join_key_attributes_);
   DeviceBuffer count(8);
   const std::size_t bitmap_bytes = static_cast<std::size_t>((n + 63) / 64) * 8 + 8;
-  // existence_map of the LIPFilterAdaptiveProber (:462-470): the probe tuples this work order looks at
-  struct LipBitmap {
-    void *ptr = nullptr;
-    ~LipBitmap() { qsx_device_free(ptr); }
-  } lip_holder;
-  if (lip_filter_adaptive_prober_ != nullptr) lip_holder.ptr = lip_filter_adaptive_prober_->filterValueAccessor(*probe, nullptr, nullptr);
-  const std::uint64_t *lip = static_cast<const std::uint64_t *>(lip_holder.ptr);
+  // ---- about and lookup ----
+  // existence_map of the LIPFilterAdaptiveProber (:462-470): `about` = the probe tuples this work order is about
+  DeviceAllocation lip_storage;
+  if (lip_filter_adaptive_prober_ != nullptr) lip_storage.ptr = lip_filter_adaptive_prober_->filterValueAccessor(block, nullptr, nullptr);
+  const std::uint64_t *about = static_cast<const std::uint64_t *>(lip_storage.ptr);
   // check_for_null_keys: a probe tuple with a NULL key component is not looked up (HashTable.hpp:2158-2160, 1855-1865):
   // it matches nothing — out of an inner / semi join, NULL-padded in an outer join, kept by an anti join.
-  // `lookup` = the tuples that are looked up, `lip` stays the set of tuples this work order is about.
-  const std::unique_ptr<DeviceBuffer> not_null_keys = NotNullFilter(*probe, join_key_attributes_, lip);
-  const std::uint64_t *lookup = not_null_keys != nullptr ? static_cast<const std::uint64_t *>(not_null_keys->ptr) : lip;
-  const bool pairs_needed = join_type_ == JoinType::kInnerJoin || join_type_ == JoinType::kLeftOuterJoin ||
-                            residual_predicate_ != nullptr || !keys.exact;
+  const std::unique_ptr<DeviceBuffer> not_null_keys = NotNullFilter(block, join_key_attributes_, about);
+  const std::uint64_t *lookup = not_null_keys != nullptr ? static_cast<const std::uint64_t *>(not_null_keys->ptr) : about;
+  const bool pairs_needed = !existence || residual_predicate_ != nullptr || !keys.exact;
+  const JoinOutput to{selection_, is_selection_on_build_, output_destination_, getPartitionId()};
 
+  // ---- the pair route's pairs ----
   JoinedPairs pairs;
   std::unique_ptr<BuildSegments> build;
   if (pairs_needed) {
     // hash_table_.getAllFromValueAccessor[CompositeKey](accessor, key(s), nullable, &collector) (:480-485)
+    // (block form only: a counting pass sizes the pair lists; the run form probes with room for one match per tuple)
     CheckStatus(qsx_join_probe_count(hash_table_, keys.ptr, n, lookup, static_cast<std::int64_t *>(count.ptr), CurrentStream()),
                 "qsx_join_probe_count");
     pairs.count = ReadCount(count.ptr);
@@ -664,101 +642,28 @@ void HashInnerJoinWorkOrder::executeBlock(block_id probe_block_id) {
                                static_cast<std::int32_t *>(pairs.probe_tids->ptr), static_cast<std::int32_t *>(pairs.build_tids->ptr),
                                pairs.count, static_cast<std::int64_t *>(count.ptr), CurrentStream()), "qsx_join_probe");
     build.reset(new BuildSegments(build_relation_, storage_manager_));
-
-    // Terms evaluated on the pairs: the component equalities of a hashed composite key
-    // (compositeKeyCollisionCheck, SeparateChainingHashTable.hpp:1046) and the residual predicate
-    // (matchesForJoinedTuples, :510-524), chained through the filter bitmap like a conjunction.
-    std::vector<ComparisonPredicate> terms;
-    if (!keys.exact) {
-      for (std::size_t k = 0; k < join_key_attributes_.size(); ++k) {
-        terms.push_back(ComparisonPredicate::Attributes(join_key_attributes_[k], false, ComparisonID::kEqual,
-                                                        build_key_attributes_[k], true));
-      }
-    }
-    if (residual_predicate_ != nullptr) {
-      terms.insert(terms.end(), residual_predicate_->conjuncts.begin(), residual_predicate_->conjuncts.end());
-    }
-    if (!terms.empty() && pairs.count > 0) {
-      const std::int64_t m = pairs.count;
-      const std::size_t pair_bitmap_bytes = static_cast<std::size_t>((m + 63) / 64) * 8 + 8;
-      std::size_t widest = 8;
-      for (const ComparisonPredicate &term : terms) {
-        widest = std::max<std::size_t>(widest, (term.on_build_side ? build_relation_ : probe_relation_).getAttributeType(term.attribute).width);
-      }
-      DeviceBuffer current(pair_bitmap_bytes), next(pair_bitmap_bytes), lhs(static_cast<std::size_t>(m) * widest + 8),
-          rhs(static_cast<std::size_t>(m) * 8 + 8);
-      void *cur = current.ptr, *nxt = next.ptr;
-      bool first = true;
-      auto gather_side = [&](attribute_id attr, bool on_build, void *dst) -> Type {
-        const Type t = (on_build ? build_relation_ : probe_relation_).getAttributeType(attr);
-        if (on_build) {
-          build->gather(attr, t.width, pairs.build_tids->ptr, m, dst);
-        } else {
-          CheckStatus(qsx_gather(t.width, probe->stripe(attr), static_cast<const std::int32_t *>(pairs.probe_tids->ptr), m, dst,
-                                 CurrentStream()), "qsx_gather");
-        }
-        return t;
-      };
-      for (const ComparisonPredicate &term : terms) {
-        if (IsLikeComparison(term.comparison)) CheckLikeTerm(term, (term.on_build_side ? build_relation_ : probe_relation_).getAttributeType(term.attribute));
-        const Type t = gather_side(term.attribute, term.on_build_side, lhs.ptr);
-        if (term.rhs_attribute != kInvalidAttributeID) {
-          if (t.id == kChar || t.id == kVarChar) {
-            throw ExecutionError("join predicate compares two string attributes (only string = literal is supported)", QSX_ERR_UNSUPPORTED);
-          }
-          const Type rt = gather_side(term.rhs_attribute, term.rhs_on_build_side, rhs.ptr);
-          if (rt.id != t.id) throw ExecutionError("join predicate compares attributes of different types", QSX_ERR_UNSUPPORTED);
-          CheckStatus(qsx_select_cmp_columns(t.id, lhs.ptr, rhs.ptr, m, static_cast<int>(term.comparison),
-                                             first ? nullptr : static_cast<const std::uint64_t *>(cur),
-                                             static_cast<std::uint64_t *>(nxt), nullptr, CurrentStream()),
-                      "qsx_select_cmp_columns");
-        } else if (t.id == kChar) {
-          SelectCharTerm(term, lhs.ptr, t.width, m, first ? nullptr : static_cast<const std::uint64_t *>(cur), static_cast<std::uint64_t *>(nxt), nullptr);
-        } else {
-          CheckStatus(qsx_select_cmp(t.id, lhs.ptr, m, static_cast<int>(term.comparison), &term.literal.v,
-                                     first ? nullptr : static_cast<const std::uint64_t *>(cur),
-                                     static_cast<std::uint64_t *>(nxt), nullptr, CurrentStream()), "qsx_select_cmp");
-        }
-        std::swap(cur, nxt);
-        first = false;
-      }
-      CompactPairs(&pairs, cur);
-    }
+    FilterPairs(probe, *build, PairTerms(join_key_attributes_, build_key_attributes_, !keys.exact, residual_predicate_), &pairs);
   }
 
-  if (join_type_ == JoinType::kLeftSemiJoin || join_type_ == JoinType::kLeftAntiJoin) {
+  if (existence) {
     // HashSemiJoinWorkOrder / HashAntiJoinWorkOrder (:680-877, :880-1000): the probe tuples with
     // (semi) / without (anti) a surviving match, projected on the probe attributes.
-    const bool anti = join_type_ == JoinType::kLeftAntiJoin;
+    // (block form only: the output goes through qsx_compact_gather + ProjectNullBitmaps, not through EmitSelectedRun)
     DeviceBuffer bitmap(bitmap_bytes);
+    std::uint64_t *found = static_cast<std::uint64_t *>(bitmap.ptr);
     if (pairs_needed) {
-      CheckStatus(qsx_tids_to_bitmap(static_cast<const std::int32_t *>(pairs.probe_tids->ptr), pairs.count, 0, n,
-                                     static_cast<std::uint64_t *>(bitmap.ptr), CurrentStream()), "qsx_tids_to_bitmap");
-      if (anti) {
-        CheckStatus(qsx_bitmap_combine(3, static_cast<const std::uint64_t *>(bitmap.ptr), nullptr, n,
-                                       static_cast<std::uint64_t *>(bitmap.ptr), CurrentStream()), "qsx_bitmap_combine");
-        if (lip != nullptr) {
-          CheckStatus(qsx_bitmap_combine(0, static_cast<const std::uint64_t *>(bitmap.ptr), lip, n,
-                                         static_cast<std::uint64_t *>(bitmap.ptr), CurrentStream()), "qsx_bitmap_combine");
-        }
-      }
-      CheckStatus(qsx_bitmap_count(static_cast<const std::uint64_t *>(bitmap.ptr), n, static_cast<std::int64_t *>(count.ptr),
-                                   CurrentStream()), "qsx_bitmap_count");
-    } else if (anti && lookup != lip) {
+      CheckStatus(qsx_tids_to_bitmap(static_cast<const std::int32_t *>(pairs.probe_tids->ptr), pairs.count, 0, n, found, CurrentStream()),
+                  "qsx_tids_to_bitmap");
+      if (anti) ComplementAmong(found, about, n);
+      CheckStatus(qsx_bitmap_count(found, n, static_cast<std::int64_t *>(count.ptr), CurrentStream()), "qsx_bitmap_count");
+    } else if (anti && lookup != about) {
       // NULL keys are not looked up and therefore survive the anti join: tuples \ (looked-up tuples with a match)
-      CheckStatus(qsx_join_probe_exists(hash_table_, keys.ptr, n, lookup, 0, static_cast<std::uint64_t *>(bitmap.ptr),
-                                        static_cast<std::int64_t *>(count.ptr), CurrentStream()), "qsx_join_probe_exists");
-      CheckStatus(qsx_bitmap_combine(3, static_cast<const std::uint64_t *>(bitmap.ptr), nullptr, n,
-                                     static_cast<std::uint64_t *>(bitmap.ptr), CurrentStream()), "qsx_bitmap_combine");
-      if (lip != nullptr) {
-        CheckStatus(qsx_bitmap_combine(0, static_cast<const std::uint64_t *>(bitmap.ptr), lip, n,
-                                       static_cast<std::uint64_t *>(bitmap.ptr), CurrentStream()), "qsx_bitmap_combine");
-      }
-      CheckStatus(qsx_bitmap_count(static_cast<const std::uint64_t *>(bitmap.ptr), n, static_cast<std::int64_t *>(count.ptr),
-                                   CurrentStream()), "qsx_bitmap_count");
+      CheckStatus(qsx_join_probe_exists(hash_table_, keys.ptr, n, lookup, 0, found, static_cast<std::int64_t *>(count.ptr), CurrentStream()),
+                  "qsx_join_probe_exists");
+      ComplementAmong(found, about, n);
+      CheckStatus(qsx_bitmap_count(found, n, static_cast<std::int64_t *>(count.ptr), CurrentStream()), "qsx_bitmap_count");
     } else {
-      CheckStatus(qsx_join_probe_exists(hash_table_, keys.ptr, n, lookup, anti ? 1 : 0,
-                                        static_cast<std::uint64_t *>(bitmap.ptr), static_cast<std::int64_t *>(count.ptr),
+      CheckStatus(qsx_join_probe_exists(hash_table_, keys.ptr, n, lookup, anti ? 1 : 0, found, static_cast<std::int64_t *>(count.ptr),
                                         CurrentStream()), "qsx_join_probe_exists");
     }
     const std::int64_t matches = ReadCount(count.ptr);
@@ -768,105 +673,38 @@ void HashInnerJoinWorkOrder::executeBlock(block_id probe_block_id) {
     std::vector<void *> dst;
     std::vector<std::int32_t> widths;
     for (std::size_t i = 0; i < selection_.size(); ++i) {
-      src.push_back(probe->stripe(selection_[i]));
+      src.push_back(block.stripe(selection_[i]));
       dst.push_back(out->stripe(static_cast<attribute_id>(i)));
       widths.push_back(probe_relation_.getAttributeType(selection_[i]).width);
     }
     const std::size_t ws_bytes = qsx_compact_workspace_bytes(n);
     DeviceBuffer ws(ws_bytes);
-    CheckStatus(qsx_compact_gather(static_cast<int>(src.size()), src.data(), widths.data(),
-                                   static_cast<const std::uint64_t *>(bitmap.ptr), n, dst.data(),
+    CheckStatus(qsx_compact_gather(static_cast<int>(src.size()), src.data(), widths.data(), found, n, dst.data(),
                                    static_cast<std::int64_t *>(count.ptr), ws.ptr, ws_bytes, CurrentStream()),
                 "qsx_compact_gather");
     const std::int64_t written = ReadCount(count.ptr);
-    ProjectNullBitmaps(*probe, selection_, bitmap.ptr, written, out.get());
+    ProjectNullBitmaps(block, selection_, bitmap.ptr, written, out.get());
     output_destination_->returnBlock(out_id, written, getPartitionId());
     return;
   }
 
-  // Inner / left outer: matched pairs first, then (outer) the probe tuples without a match with
-  // NULL build-side attributes (HashOuterJoinWorkOrder, :1026-1099).
-  const std::int64_t matches = pairs.count;
+  // Inner / left outer: the pairs, and (outer) the probe tuples among `about` that have none
   std::int64_t unmatched = 0;
   std::unique_ptr<DeviceBuffer> unmatched_tids;
   if (join_type_ == JoinType::kLeftOuterJoin) {
     DeviceBuffer bitmap(bitmap_bytes);
-    CheckStatus(qsx_tids_to_bitmap(static_cast<const std::int32_t *>(pairs.probe_tids->ptr), matches, 0, n,
-                                   static_cast<std::uint64_t *>(bitmap.ptr), CurrentStream()), "qsx_tids_to_bitmap");
-    CheckStatus(qsx_bitmap_combine(3, static_cast<const std::uint64_t *>(bitmap.ptr), nullptr, n,
-                                   static_cast<std::uint64_t *>(bitmap.ptr), CurrentStream()), "qsx_bitmap_combine");
-    if (lip != nullptr) {
-      CheckStatus(qsx_bitmap_combine(0, static_cast<const std::uint64_t *>(bitmap.ptr), lip, n,
-                                     static_cast<std::uint64_t *>(bitmap.ptr), CurrentStream()), "qsx_bitmap_combine");
-    }
+    std::uint64_t *found = static_cast<std::uint64_t *>(bitmap.ptr);
+    CheckStatus(qsx_tids_to_bitmap(static_cast<const std::int32_t *>(pairs.probe_tids->ptr), pairs.count, 0, n, found, CurrentStream()),
+                "qsx_tids_to_bitmap");
+    ComplementAmong(found, about, n);   // (`about`, not `lookup`: a tuple with a NULL key is NULL-padded, not dropped)
     unmatched_tids.reset(new DeviceBuffer(static_cast<std::size_t>(n) * 4 + 8));
     const std::size_t ws_bytes = qsx_compact_workspace_bytes(n);
     DeviceBuffer ws(ws_bytes);
-    CheckStatus(qsx_bitmap_to_tids(static_cast<const std::uint64_t *>(bitmap.ptr), n, 0, static_cast<std::int32_t *>(unmatched_tids->ptr),
+    CheckStatus(qsx_bitmap_to_tids(found, n, 0, static_cast<std::int32_t *>(unmatched_tids->ptr),
                                    static_cast<std::int64_t *>(count.ptr), ws.ptr, ws_bytes, CurrentStream()), "qsx_bitmap_to_tids");
     unmatched = ReadCount(count.ptr);
   }
-  const std::int64_t total = matches + unmatched;
-  block_id out_id;
-  BlockReference out = output_destination_->getBlockForInsertion(total > 0 ? total : 1, &out_id);
-  // Row numbers of all `total` output rows per side, for the null bits: pairs first, then (outer) the unmatched probe
-  // tuples next to build tid -1 = NULL padding.  Only materialised when some output attribute can be NULL.
-  std::unique_ptr<DeviceBuffer> all_probe_tids, all_build_tids;
-  auto all_tids = [&](bool on_build) -> const void * {
-    std::unique_ptr<DeviceBuffer> &buf = on_build ? all_build_tids : all_probe_tids;
-    if (unmatched == 0) return on_build ? pairs.build_tids->ptr : pairs.probe_tids->ptr;
-    if (buf == nullptr) {
-      buf.reset(new DeviceBuffer(static_cast<std::size_t>(total) * 4 + 8));
-      char *tail = static_cast<char *>(buf->ptr) + static_cast<std::size_t>(matches) * 4;
-      CheckStatus(qsx_copy_on_device(buf->ptr, on_build ? pairs.build_tids->ptr : pairs.probe_tids->ptr,
-                                     static_cast<std::size_t>(matches) * 4, CurrentStream()), "qsx_copy_on_device");
-      if (on_build) {
-        CheckStatus(qsx_memset_device(tail, 0xFF, static_cast<std::size_t>(unmatched) * 4, CurrentStream()), "qsx_memset_device");
-      } else {
-        CheckStatus(qsx_copy_on_device(tail, unmatched_tids->ptr, static_cast<std::size_t>(unmatched) * 4, CurrentStream()),
-                    "qsx_copy_on_device");
-      }
-    }
-    return buf->ptr;
-  };
-  for (std::size_t i = 0; i < selection_.size(); ++i) {
-    // Scalar::getAllValuesForJoin (:529-536)
-    char *dst = static_cast<char *>(out->stripe(static_cast<attribute_id>(i)));
-    const bool on_build = is_selection_on_build_[i];
-    const int width = (on_build ? build_relation_ : probe_relation_).getAttributeType(selection_[i]).width;
-    if (on_build) {
-      build->gather(selection_[i], width, pairs.build_tids->ptr, matches, dst);
-    } else {
-      CheckStatus(qsx_gather(width, probe->stripe(selection_[i]), static_cast<const std::int32_t *>(pairs.probe_tids->ptr), matches,
-                             dst, CurrentStream()), "qsx_gather");
-    }
-    if (unmatched > 0) {
-      char *tail = dst + static_cast<std::size_t>(matches) * width;
-      if (on_build) {
-        // result->fillWithNulls() (:1077-1080): zero bytes here, the null bits of rows [matches, total) below
-        CheckStatus(qsx_memset_device(tail, 0, static_cast<std::size_t>(unmatched) * width, CurrentStream()), "qsx_memset_device");
-        if (out->nullBitmap(static_cast<attribute_id>(i)) == nullptr) {
-          throw ExecutionError("outer join output attribute taken from the build side must be nullable", QSX_ERR_INVALID_ARGUMENT);
-        }
-      } else {
-        CheckStatus(qsx_gather(width, probe->stripe(selection_[i]), static_cast<const std::int32_t *>(unmatched_tids->ptr), unmatched,
-                               tail, CurrentStream()), "qsx_gather");
-      }
-    }
-    // null bits of the output attribute: the source attribute's bits at the joined rows, 1 under the outer join's padding
-    const bool source_nullable = (on_build ? build_relation_ : probe_relation_).getAttributeType(selection_[i]).nullable;
-    if (total > 0 && (source_nullable || (on_build && unmatched > 0))) {
-      std::uint64_t *nulls = out->nullBitmap(static_cast<attribute_id>(i));
-      if (nulls == nullptr) throw ExecutionError("join output of a nullable attribute must be nullable", QSX_ERR_INVALID_ARGUMENT);
-      if (on_build) {
-        build->gatherNulls(selection_[i], all_tids(true), total, nulls);
-      } else {
-        GatherBlockNulls(*probe, selection_[i], all_tids(false), total, nulls);
-      }
-    }
-  }
-  CheckStatus(qsx_stream_synchronize(CurrentStream()), "qsx_stream_synchronize");
-  output_destination_->returnBlock(out_id, total, getPartitionId());  // output_destination_->bulkInsertTuples(&temp_result) (:539)
+  EmitPairs(to, probe, *build, pairs, unmatched_tids.get(), unmatched);
 }
 
 namespace {

@@ -133,6 +133,54 @@ struct DeviceBuffer {
 std::int64_t ReadCount(const void *dev_count);
 std::uint64_t NowMicros();
 
+// A pointer from qsx_device_alloc that a callee hands out (the bitmaps of a LIPFilterAdaptiveProber), freed at scope exit.
+struct DeviceAllocation {
+  void *ptr = nullptr;
+  DeviceAllocation() = default;
+  ~DeviceAllocation() { qsx_device_free(ptr); }
+  DeviceAllocation(const DeviceAllocation &) = delete;
+  DeviceAllocation &operator=(const DeviceAllocation &) = delete;
+};
+
+// The selected tuples of a run of blocks, block after block, compacted into ONE output block of `destination` with room for
+// `capacity` tuples (one qsx_compact_gather_blocks): output attribute i takes attribute selection[i], bitmaps[b] selects block
+// b's tuples (nullptr as a whole: every tuple).  want_tids: also the tuple id of every output tuple — base_tids[b] + row, or
+// the run-global row number without base_tids — for the null bits that follow the values.  Waits for the count (ReadCount
+// on count_dev); the block is the caller's to return.  The workspace and the tuple ids travel with the result: scratch of a
+// megabyte waits for the stream when it goes, so it goes when the caller is done, not in between the caller's launches.
+struct CompactedRun {
+  BlockReference out;
+  block_id out_id = 0;
+  std::int64_t written = 0;
+  std::unique_ptr<DeviceBuffer> workspace, tids;
+};
+inline CompactedRun CompactRunInto(const std::vector<BlockReference> &blocks, const std::vector<std::int64_t> &rows,
+                                   const std::vector<attribute_id> &selection, const std::uint64_t *const *bitmaps,
+                                   const std::int32_t *base_tids, std::int64_t capacity, bool want_tids,
+                                   InsertDestination *destination, void *count_dev) {
+  CompactedRun run;
+  const std::size_t nb = blocks.size(), nc = selection.size();
+  run.out = destination->getBlockForInsertion(capacity > 0 ? capacity : 1, &run.out_id);
+  std::vector<const void *> src(nb * nc);
+  std::vector<void *> dst;
+  std::vector<std::int32_t> widths;
+  for (std::size_t i = 0; i < nc; ++i) {
+    dst.push_back(run.out->stripe(static_cast<attribute_id>(i)));
+    widths.push_back(blocks.front()->getRelation().getAttributeType(selection[i]).width);
+    for (std::size_t b = 0; b < nb; ++b) src[b * nc + i] = blocks[b]->stripe(selection[i]);
+  }
+  const std::size_t ws_bytes = qsx_compact_blocks_workspace_bytes(static_cast<std::int64_t>(nb), rows.data());
+  run.workspace.reset(new DeviceBuffer(ws_bytes + 8));
+  if (want_tids) run.tids.reset(new DeviceBuffer(static_cast<std::size_t>(capacity > 0 ? capacity : 1) * 4 + 8));
+  CheckStatus(qsx_compact_gather_blocks(static_cast<int>(nc), widths.data(), static_cast<std::int64_t>(nb), rows.data(), src.data(), bitmaps,
+                                        want_tids ? base_tids : nullptr, dst.data(),
+                                        want_tids ? static_cast<std::int32_t *>(run.tids->ptr) : nullptr,
+                                        static_cast<std::int64_t *>(count_dev), run.workspace->ptr, ws_bytes, CurrentStream()),
+              "qsx_compact_gather_blocks");
+  run.written = ReadCount(count_dev);   // (synchronises the stream: the block's tuples are written)
+  return run;
+}
+
 // NULL handling shared by the aggregation state and the operators (storage.cpp)
 std::unique_ptr<DeviceBuffer> NotNullFilter(const StorageBlock &block, const std::vector<attribute_id> &attrs, const std::uint64_t *filter);
 void GatherBlockNulls(const StorageBlock &block, attribute_id attr, const void *tids, std::int64_t n, std::uint64_t *dst);

@@ -119,10 +119,7 @@ bool SelectWorkOrder::executeRun() {
   const std::size_t nb = blocks.size();
   // SelectOperator.cpp:161-195: predicate matches, then the LIP filters on what is left (a filter looks a tuple up at a random
   // place of its bit vector; a tuple the predicate dropped costs it nothing: Q3's lineitem Select loses 46 % of its lookups)
-  struct OwnedStorage {
-    void *ptr = nullptr;
-    ~OwnedStorage() { qsx_device_free(ptr); }
-  } lip_storage;
+  DeviceAllocation lip_storage;
   std::vector<const std::uint64_t *> lip_bitmaps;
   std::int64_t lip_hits = 0;
   RunMatches run_matches;
@@ -171,24 +168,10 @@ bool SelectWorkOrder::executeRun() {
     for (std::int64_t m : block_matches) matches += m;
     selected = reinterpret_cast<const std::uint64_t *const *>(run_matches.bitmaps.data());
   }
-  block_id out_id;
-  BlockReference out = output_destination_->getBlockForInsertion(matches > 0 ? matches : 1, &out_id);
-  std::vector<const void *> src(nb * selection.size());
-  std::vector<void *> dst;
-  std::vector<std::int32_t> widths;
-  for (std::size_t i = 0; i < selection.size(); ++i) {
-    dst.push_back(out->stripe(static_cast<attribute_id>(i)));
-    widths.push_back(blocks.front()->getRelation().getAttributeType(selection[i]).width);
-    for (std::size_t b = 0; b < nb; ++b) src[b * selection.size() + i] = blocks[b]->stripe(selection[i]);
-  }
-  const std::size_t ws_bytes = qsx_compact_blocks_workspace_bytes(static_cast<std::int64_t>(nb), rows.data());
-  DeviceBuffer ws(ws_bytes + 8), count(8);
-  CheckStatus(qsx_compact_gather_blocks(static_cast<int>(selection.size()), widths.data(), static_cast<std::int64_t>(nb), rows.data(),
-                                        src.data(), selected, nullptr, dst.data(),
-                                        nullptr, static_cast<std::int64_t *>(count.ptr), ws.ptr, ws_bytes, CurrentStream()),
-              "qsx_compact_gather_blocks");
-  const std::int64_t written = ReadCount(count.ptr);   // synchronises the work order, like the reference's execute()
-  output_destination_->returnBlock(out_id, written, getPartitionId());
+  DeviceBuffer count(8);
+  const CompactedRun compacted = CompactRunInto(blocks, rows, selection, selected, nullptr, matches, /*want_tids=*/false, output_destination_, count.ptr);
+  // (CompactRunInto's wait for the count synchronises the work order, like the reference's execute())
+  output_destination_->returnBlock(compacted.out_id, compacted.written, getPartitionId());
   return true;
 }
 

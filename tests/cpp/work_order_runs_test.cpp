@@ -87,10 +87,11 @@ double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-// A LIP filter over l_orderkey holding the keys below kLipLimit, built by a BuildHashOperator over a relation of those keys
-// (in 10 blocks; the build runs in the run form too).
+// A LIP filter over probe_attribute (l_orderkey in most cases) holding the keys below kLipLimit, built by a BuildHashOperator
+// over a relation of those keys (in 10 blocks; the build runs in the run form too).
 constexpr std::int32_t kLipLimit = 150000;
-QueryContext::lip_deployment_id deployLip(QueryContext *ctx, StorageManager *storage, CatalogRelation *small, std::size_t blocks_per_order) {
+QueryContext::lip_deployment_id deployLip(QueryContext *ctx, StorageManager *storage, CatalogRelation *small, std::size_t blocks_per_order,
+                                          attribute_id probe_attribute) {
   small->addAttribute("k", Type::Int());
   std::vector<std::int32_t> ks(kLipLimit);
   for (std::int32_t i = 0; i < kLipLimit; ++i) ks[i] = i;
@@ -98,7 +99,7 @@ QueryContext::lip_deployment_id deployLip(QueryContext *ctx, StorageManager *sto
   const auto filter = ctx->addLIPFilter(QSX_LIP_BITVECTOR_EXACT, kLipLimit, 0);
   QueryContext::LIPFilterDeployment build_dep, probe_dep;
   build_dep.build_entries.push_back({filter, 0});
-  probe_dep.probe_entries.push_back({filter, 0});   // l_orderkey
+  probe_dep.probe_entries.push_back({filter, probe_attribute});
   const auto build_id = ctx->addLIPDeployment(build_dep);
   const auto probe_id = ctx->addLIPDeployment(probe_dep);
   const auto table = ctx->addJoinHashTable(kInt, kLipLimit);
@@ -126,7 +127,7 @@ Rows runSelect(bool nullable_quantity, std::size_t blocks_per_order, std::size_t
   const auto pred = ctx.addPredicate(p);
   const auto dest = ctx.addInsertDestination(&out, &storage);
   SelectOperator op(0, li.rel, false, out, dest, pred, std::vector<attribute_id>{0, 2}, true);
-  if (with_lip) op.deployLIPFilters(deployLip(&ctx, &storage, &small, blocks_per_order));
+  if (with_lip) op.deployLIPFilters(deployLip(&ctx, &storage, &small, blocks_per_order, /*l_orderkey*/ 0));
   op.setBlocksPerWorkOrder(blocks_per_order);
   const double t0 = now_ms();
   fetchAndExecuteWorkOrders(&op, &ctx, &storage);
@@ -174,7 +175,7 @@ Rows runJoin(bool exact_stats, std::size_t blocks_per_order, std::size_t *out_bl
   BuildHashOperator builder(0, orders, true, {0}, false, 1, table);
   HashJoinOperator prober(0, orders, li.rel, true, {0}, false, 1, false, out, dest, table, QueryContext::kInvalidPredicateId, selection,
                           &on_build, HashJoinOperator::JoinType::kInnerJoin);
-  if (with_lip) prober.deployLIPFilters(deployLip(&ctx, &storage, &small, blocks_per_order));
+  if (with_lip) prober.deployLIPFilters(deployLip(&ctx, &storage, &small, blocks_per_order, /*l_orderkey*/ 0));
   prober.setBlocksPerWorkOrder(blocks_per_order);
   builder.setBlocksPerWorkOrder(blocks_per_order);
   const double tb = now_ms();
@@ -298,7 +299,7 @@ void runSemiAntiResidual(bool anti, bool exact_stats, std::size_t blocks_per_ord
                           anti ? HashJoinOperator::JoinType::kLeftAntiJoin : HashJoinOperator::JoinType::kLeftSemiJoin);
   // under a LIP filter the work order is only ABOUT the tuples the filter lets through: an anti join must not bring the
   // others back through the complement of the paired tuples
-  if (with_lip) prober.deployLIPFilters(deployLip(&ctx, &storage, &small, blocks_per_order));
+  if (with_lip) prober.deployLIPFilters(deployLip(&ctx, &storage, &small, blocks_per_order, /*l_orderkey*/ 0));
   prober.setBlocksPerWorkOrder(blocks_per_order);
   builder.setBlocksPerWorkOrder(blocks_per_order);
   fetchAndExecuteWorkOrders(&builder, &ctx, &storage);
@@ -464,13 +465,19 @@ void runJoinCharResidual(std::size_t blocks_per_order, std::size_t *out_blocks) 
 // with a NULL key is not looked up (HashTable.hpp:2158-2160): out of an inner / semi join, kept by an anti join, NULL-padded
 // by an outer join; the null bits of the projected probe attribute follow the output tuples.  Tuples as (quantity or -1 for
 // NULL, second attribute or a marker for NULL).
-void runNullableProbeSide(HashJoinOperator::JoinType type, bool exact_stats, std::size_t blocks_per_order, std::size_t *out_blocks) {
+// with_lip: a LIP filter on the probe side as well.  The work order is then ABOUT the tuples the filter lets through and LOOKS UP
+// those of them whose key is not NULL — two different sets: an anti join keeps, and an outer join pads, the tuples it is about
+// and did not find, the NULL keys among them, and none of those the filter rejected.  The filter sits on a fourth, non-nullable
+// attribute l_tag (below kLipLimit: passes), since the run form refuses a filter on an attribute with a null bitmap.
+void runNullableProbeSide(HashJoinOperator::JoinType type, bool exact_stats, std::size_t blocks_per_order, std::size_t *out_blocks,
+                          bool with_lip = false) {
   using JoinType = HashJoinOperator::JoinType;
   StorageManager storage;
-  CatalogRelation li(1, "lineitem"), orders(3, "orders"), out(4, "joined");
+  CatalogRelation li(1, "lineitem"), orders(3, "orders"), out(4, "joined"), small(7, "small");
   li.addAttribute("l_orderkey", Type::Int().getNullableVersion());
   li.addAttribute("l_quantity", Type::Int().getNullableVersion());
   li.addAttribute("l_extendedprice", Type::Double());
+  if (with_lip) li.addAttribute("l_tag", Type::Int());
   orders.addAttribute("o_orderkey", Type::Int());
   const bool existence = type == JoinType::kLeftSemiJoin || type == JoinType::kLeftAntiJoin;
   out.addAttribute("l_quantity", Type::Int().getNullableVersion());
@@ -481,16 +488,18 @@ void runNullableProbeSide(HashJoinOperator::JoinType type, bool exact_stats, std
   std::mt19937_64 rng(23);
   for (int b = 0; b < kBlocks; ++b) {
     const std::int64_t n = b == 5 ? 0 : kBlockRows - 13 * (b % 7);
-    std::vector<std::int32_t> k(n), q(n);
+    std::vector<std::int32_t> k(n), q(n), tag(n);
     std::vector<double> p(n);
     std::vector<std::uint64_t> key_nulls(static_cast<std::size_t>((n + 63) / 64) + 1, 0), qty_nulls(key_nulls.size(), 0);
     for (std::int64_t i = 0; i < n; ++i) {
       k[i] = static_cast<std::int32_t>(rng() % 300000);
       q[i] = static_cast<std::int32_t>(rng() % 50) + 1;
       p[i] = static_cast<double>(rng() % 10000000);
+      if (with_lip) tag[i] = static_cast<std::int32_t>(rng() % 300000);
       const bool key_null = (b & 1) != 0 && i % 11 == 0, qty_null = i % 17 == 0;
       if (key_null) key_nulls[i >> 6] |= 1ull << (63 - (i & 63));
       if (qty_null) qty_nulls[i >> 6] |= 1ull << (63 - (i & 63));
+      if (with_lip && tag[i] >= kLipLimit) continue;   // not among the tuples the work order is about: in no join's output
       const bool matched = !key_null && k[i] < 200000 && (k[i] & 1) == 0;
       const std::int64_t qty = qty_null ? -1 : q[i];
       switch (type) {
@@ -500,8 +509,13 @@ void runNullableProbeSide(HashJoinOperator::JoinType type, bool exact_stats, std
         default: want.emplace_back(qty, matched ? k[i] : kNullMark); break;
       }
     }
-    const std::vector<const std::uint64_t *> null_bitmaps = {(b & 1) != 0 ? key_nulls.data() : nullptr, qty_nulls.data(), nullptr};
-    storage.loadBlock(&li, {k.data(), q.data(), p.data()}, n, 0, nullptr, &null_bitmaps);
+    std::vector<const void *> columns = {k.data(), q.data(), p.data()};
+    std::vector<const std::uint64_t *> null_bitmaps = {(b & 1) != 0 ? key_nulls.data() : nullptr, qty_nulls.data(), nullptr};
+    if (with_lip) {
+      columns.push_back(tag.data());
+      null_bitmaps.push_back(nullptr);
+    }
+    storage.loadBlock(&li, columns, n, 0, nullptr, &null_bitmaps);
   }
   std::vector<std::int32_t> okeys;
   for (std::int32_t k = 0; k < 200000; k += 2) okeys.push_back(k);
@@ -515,6 +529,7 @@ void runNullableProbeSide(HashJoinOperator::JoinType type, bool exact_stats, std
   const std::vector<bool> on_build = existence ? std::vector<bool>{false, false} : std::vector<bool>{false, true};
   BuildHashOperator builder(0, orders, true, {0}, false, 1, table);
   HashJoinOperator prober(0, orders, li, true, {0}, true, 1, false, out, dest, table, QueryContext::kInvalidPredicateId, selection, &on_build, type);
+  if (with_lip) prober.deployLIPFilters(deployLip(&ctx, &storage, &small, blocks_per_order, /*l_tag*/ 3));
   prober.setBlocksPerWorkOrder(blocks_per_order);
   fetchAndExecuteWorkOrders(&builder, &ctx, &storage);
   fetchAndExecuteWorkOrders(&prober, &ctx, &storage);
@@ -766,6 +781,16 @@ int main() {
       EXPECT_EQ(one, static_cast<std::size_t>(kBlocks));
       EXPECT_EQ(run, static_cast<std::size_t>((kBlocks + 63) / 64));
     }
+  }
+  // ... and the same under a LIP filter on another probe attribute: the tuples a work order is about and the tuples it looks up
+  // are both there and differ (the complement of an anti / outer join is taken among the former)
+  for (const HashJoinOperator::JoinType type : {HashJoinOperator::JoinType::kInnerJoin, HashJoinOperator::JoinType::kLeftSemiJoin,
+                                                HashJoinOperator::JoinType::kLeftAntiJoin, HashJoinOperator::JoinType::kLeftOuterJoin}) {
+    std::size_t one = 0, run = 0;
+    runNullableProbeSide(type, true, 1, &one, /*with_lip=*/true);
+    runNullableProbeSide(type, true, 64, &run, /*with_lip=*/true);
+    EXPECT_EQ(one, static_cast<std::size_t>(kBlocks));
+    EXPECT_EQ(run, static_cast<std::size_t>((kBlocks + 63) / 64));
   }
   // an anti / semi join with a residual predicate UNDER A LIP FILTER, and semi / anti joins over a hashed composite key:
   // run forms since round 4
